@@ -12,10 +12,15 @@ path has no collective; rank 0's packed weights are RCCL-broadcast once at start
 C-ABI (pwg_broadcast_weights). Default: weak scaling, every rank runs the same per-GPU batch shape.
 --strong: SURVEY.md sec 8(d)(5), the fixed 512-utterance list LPT-sharded over the ranks.
 
-At N=1 the line also carries the reference's own call pattern (B=1 inference() latency rows, LJ v1,
-bin/decode.py:236-268) and a CPU baseline on a bounded sample.
+A plain run sets up, warms up, times --steps forwards (per-launch event timing off: the path a
+caller gets), writes the last step's output when --dump-outputs DIR is given, and prints ONE JSON
+line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step).
 
-Prints ONE JSON line (rank 0) with the contract fields plus "roofline" and "cpu_baseline".
+--full adds everything else to that line, each from runs of its own: per-launch HIP-event times of
+the timed steps ("kernel_ms_per_step", "roofline", with HBM traffic from rocprofv3 --pmc passes over
+a child process), the exact-fp32 leg, the PCIe-inclusive rate, the embedded MB-MelGAN v2 / HiFiGAN v1
+runs ("vocoders"), and at N=1 the reference's own call pattern (B=1 inference() latency rows, LJ v1,
+bin/decode.py:236-268) and a CPU baseline on a bounded sample ("cpu_baseline").
 """
 
 import argparse
@@ -162,6 +167,26 @@ def per_rank_seconds(local_s, world, dev):
     ts = [torch.zeros_like(t) for _ in range(world)]
     dist.all_gather(ts, t)
     return [float(x.item()) for x in ts]
+
+
+DUMP_BUDGET_BYTES = 48 * 1024 * 1024  # --dump-outputs: all arrays together (limit: 64 MB)
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each device tensor of `arrays` ({name: tensor}, what the timed path
+    left in the caller's buffers after its last step) as path/<name>.npy, float32. An array over
+    its share of DUMP_BUDGET_BYTES is written as a fixed sample: the elements at the sorted,
+    de-duplicated indices RandomState(DUMP_SAMPLE_SEED).randint(0, n, share), the same for every
+    run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(len(arrays), 1)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.unique(np.random.RandomState(DUMP_SAMPLE_SEED).randint(0, flat.numel(), size=share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.to(torch.float32).cpu().numpy())
 
 
 PMC_PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",), ("GRBM_GUI_ACTIVE", "SQ_VALU_MFMA_BUSY_CYCLES"))
@@ -397,7 +422,7 @@ def cpu_baseline(params, sd, config, n_utts, reps=1):
     profiles/r02_cpu/cpu_crosscheck.json) on a bounded sample of the workload, B=1 per utterance
     like bin/decode.py, one warm-up call, each utterance timed `reps` times (best kept).
     BASELINE.md sec 4's protocol is the 16-utterance subset, best of 3 (`--cpu-utts 16 --cpu-reps
-    3`, ~5 min of CPU); the default bench line times 4 of those utterances once (~25 s) to stay
+    3`, ~5 min of CPU); the --full bench line times 4 of those utterances once (~25 s) to stay
     within the bench's bounded CPU sample, and says so. Returns the cpu_baseline object."""
     from oracle.pwg_torch_cpu import TorchCPUGenerator
 
@@ -632,7 +657,7 @@ def bench_vocoder(args, rank, world, dev, live_traffic=(None, "off", None, None)
     """MelGAN-family generator inference (BASELINE configs[2] multi_band_melgan.v2 and [3]
     hifigan.v1) on the conv-network executor: same ragged-batch workload shape
     as the PWG bench, weak scaling, utterance sharding, RCCL weight broadcast.
-    embedded: called from the default PWG line (N = 1): return the result object instead of
+    embedded: called from the --full PWG line (N = 1): return the result object instead of
     printing it (the line's "vocoders" object)."""
     from oracle.melgan_torch_cpu import TorchCPUVocoder  # cpu_baseline leg only
     from parallelwavegan_amd.engine import fold_weight_norm
@@ -651,13 +676,14 @@ def bench_vocoder(args, rank, world, dev, live_traffic=(None, "off", None, None)
     for _ in range(args.warmup):
         eng.run(plan, mel, out, check=False)
     torch.cuda.synchronize(dev)
-    # untimed pass with per-op timing on: its events return to the executor's pool, so the timed
-    # steps record pooled events instead of creating ~2 per op on the host between launches
-    eng.set_timing(True)
-    for _ in range(args.steps):
-        eng.run(plan, mel, out, check=False)
-    torch.cuda.synchronize(dev)
-    eng.collect_timing()
+    if args.full:
+        # untimed pass with per-op timing on: its events return to the executor's pool, so the timed
+        # steps record pooled events instead of creating ~2 per op on the host between launches
+        eng.set_timing(True)
+        for _ in range(args.steps):
+            eng.run(plan, mel, out, check=False)
+        torch.cuda.synchronize(dev)
+        eng.collect_timing()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -670,23 +696,55 @@ def bench_vocoder(args, rank, world, dev, live_traffic=(None, "off", None, None)
     local_elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(local_elapsed, dev)
     rank_seconds = per_rank_seconds(local_elapsed, world, dev) if not embedded else [local_elapsed]
-    eng.set_timing(False)
-    timing = eng.collect_timing()
+    timing = None
+    if args.full:
+        eng.set_timing(False)
+        timing = eng.collect_timing()
     if eng.split_f16:
         eng.run_status(plan)  # split-f16 range flag of the last timed run (raises when set)
     if not torch.isfinite(out).all():
         raise RuntimeError("non-finite generator output")
+    if args.dump_outputs and rank == 0 and not embedded:
+        dump_outputs(args.dump_outputs, {"audio": out})
     samples = int(lengths.sum()) * hop
     value = samples * world * args.steps / elapsed
     if rank != 0:
         if not embedded:
             dist.destroy_process_group()
         return None
+    frames = int(lengths.sum())
+    res = {
+        "metric": f"audio samples/sec/GPU ({fs / 1000:g} kHz {args.config}, 80-band mel)",
+        "value": round(value, 1),
+        "unit": "audio samples/s (whole job, all GPUs)",
+        "n_gpus": world if os.environ.get("PWG_BENCH_BACKEND", "nccl") == "nccl"
+                  else min(world, max(torch.cuda.device_count(), 1)),
+        "ranks": world,
+        "rank_seconds": [round(x, 4) for x in rank_seconds],
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32" if args.cnet_fp32 else "f32 (fp16 hi+lo pair operands, 3 f16 MFMAs per product, fp32 accumulate)",
+        "data": "synthetic (seeded N(0,1) mel, seeded N(0, 1/fan_in) weights)",
+        "config": {"workload": f"{args.config} generator inference, {args.utts} ragged utterances per GPU per step",
+                   "model": cls_name, "sampling_rate": fs, "hop": hop, "global_batch": args.utts * world,
+                   "frames_per_gpu": frames, "samples_per_step_per_gpu": samples,
+                   "parallelism": f"utterance-sharded x{world}"},
+        "x_realtime_per_gpu": round(value / world / fs, 1),
+        "range_check": "ok (pwg_cnet_run_status after the timed steps)" if eng.split_f16 else "n/a (exact fp32)",
+    }
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return None
     fl_frame = program_flops_per_frame(P)
     by_frame = program_bytes_per_frame(P)
     kern_ms = sum(ms for _, ms, _ in timing) / args.steps
     voc_bytes = live_traffic[0] and int(live_traffic[0])  # HBM bytes of one forward (rocprofv3 --pmc)
-    frames = int(lengths.sum())
     achieved = fl_frame * frames / (kern_ms * 1e-3) / 1e12
     top = sorted(timing, key=lambda r: -r[1])[:5]
     cpu = None
@@ -714,29 +772,8 @@ def bench_vocoder(args, rank, world, dev, live_traffic=(None, "off", None, None)
     lat = None
     if not args.no_latency and world == 1:
         lat = vocoder_latency_rows(m, dev)
-    res = {
-        "metric": f"audio samples/sec/GPU ({fs / 1000:g} kHz {args.config}, 80-band mel)",
-        "value": round(value, 1),
-        "unit": "audio samples/s (whole job, all GPUs)",
-        "n_gpus": world if os.environ.get("PWG_BENCH_BACKEND", "nccl") == "nccl"
-                  else min(world, max(torch.cuda.device_count(), 1)),
-        "ranks": world,
-        "rank_seconds": [round(x, 4) for x in rank_seconds],
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32" if args.cnet_fp32 else "f32 (fp16 hi+lo pair operands, 3 f16 MFMAs per product, fp32 accumulate)",
-        "data": "synthetic (seeded N(0,1) mel, seeded N(0, 1/fan_in) weights)",
-        "config": {"workload": f"{args.config} generator inference, {args.utts} ragged utterances per GPU per step",
-                   "model": cls_name, "sampling_rate": fs, "hop": hop, "global_batch": args.utts * world,
-                   "frames_per_gpu": frames, "samples_per_step_per_gpu": samples,
-                   "parallelism": f"utterance-sharded x{world}",
-                   "fused_conv_pairs": sum(1 for _, _, n in timing if n == 0)},
-        "x_realtime_per_gpu": round(value / world / fs, 1),
-        "range_check": "ok (pwg_cnet_run_status after the timed steps)" if eng.split_f16 else "n/a (exact fp32)",
+    res["config"]["fused_conv_pairs"] = sum(1 for _, _, n in timing if n == 0)
+    res.update({
         "kernel_ms_per_step": round(kern_ms, 3),
         "top_ops_ms_per_step": {n: round(ms / args.steps, 3) for n, ms, _ in top},
         "roofline": ({"kernel": "all conv ops (fp32 MFMA implicit GEMM), whole program", "bound": "mfma",
@@ -763,7 +800,7 @@ def bench_vocoder(args, rank, world, dev, live_traffic=(None, "off", None, None)
         "cpu_baseline": cpu,
         "exact_fp32": exact,
         "latency": lat,
-    }
+    })
     if embedded:
         for k in ("n_gpus", "ranks", "rank_seconds", "higher_is_better", "scaling", "vs_baseline", "data", "warmup"):
             res.pop(k, None)
@@ -774,7 +811,7 @@ def bench_vocoder(args, rank, world, dev, live_traffic=(None, "off", None, None)
         dist.destroy_process_group()
 
 
-# Vocoder configs carried in the default PWG line (BASELINE.json configs[2] and [3]).
+# Vocoder configs carried in the PWG line of a --full run (BASELINE.json configs[2] and [3]).
 EMBED_VOCODERS = ["mb_melgan_v2", "hifigan_v1"]
 
 
@@ -904,11 +941,120 @@ def latency_rows(dev, reps=20):
             "decode_loop": loop, "decode_loop_repeats": loop_rep, "rows": rows}
 
 
+def pcie_inclusive_seconds(eng, plan, mel, noise, out, steps, world, dev):
+    """--full: wall seconds (max over ranks) of `steps` forwards with the transfers included."""
+    # PCIe-inclusive rate (never `value`): host mel + noise in pinned memory -> H2D -> forward ->
+    # D2H of the audio, like inference() called on host arrays (models/parallel_wavegan.py:244-263)
+    mel_h, noise_h = mel.cpu().pin_memory(), noise.cpu().pin_memory()
+    out_h = torch.empty(out.numel(), dtype=torch.float32).pin_memory()
+    torch.cuda.synchronize(dev)
+    if world > 1:
+        dist.barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        mel.copy_(mel_h, non_blocking=True)
+        noise.copy_(noise_h, non_blocking=True)
+        eng.run(plan, mel, noise, out, check=False)
+        out_h.copy_(out, non_blocking=True)
+    torch.cuda.synchronize(dev)
+    if world > 1:
+        dist.barrier()
+    return max_over_ranks(time.perf_counter() - t0, dev)
+
+
+def layer_roofline(args, params, plan, lengths, timing, live_traffic, fuse_first):
+    """--full: the line's "roofline" object, from the per-launch HIP-event times of the timed steps
+    (`timing`) and the HBM traffic of the in-run PMC passes (`live_traffic`, else --traffic-json)."""
+    H = int(np.prod(params["upsample_params"]["upsample_scales"]))
+    layer_ms, layer_n = timing["residual_layer"]
+    layer_avg_s = layer_ms / 1e3 / max(layer_n, 1)
+    flops_launch = layer_flops_per_sample(params) * plan.total_samples
+    achieved_tflops = flops_launch / layer_avg_s / 1e12
+    traffic = mfma_insts = None
+    traffic_source = None
+    if live_traffic[0] is not None:
+        traffic, traffic_source = live_traffic[:2]
+    elif os.path.exists(args.traffic_json):
+        try:
+            tj = json.load(open(args.traffic_json))
+            if (tj.get("config") == args.config and tj.get("utts") == args.utts and not args.strong
+                    and tj.get("layer_kernel", "persistent") == args.layer_kernel):
+                traffic = tj.get("hbm_bytes_per_launch")
+                mfma_insts = tj.get("mfma_insts_per_launch")
+                traffic_source = (f"{os.path.relpath(args.traffic_json, REPO)} (rocprofv3 --pmc FETCH_SIZE x2 + "
+                                  f"WRITE_SIZE of this workload, {tj.get('source', 'committed profile')}; "
+                                  f"not measured in this run: {live_traffic[1]})")
+        except (OSError, ValueError):
+            traffic = None
+    L = params["layers"]
+    if args.layer_kernel in ("split", "split16"):
+        # HBM-bound (DESIGN.md 3.0): algorithmic bytes of the engine's layer per launch / launch time
+        bytes_launch = split_layer_bytes_per_sample(params, H, L, fuse_first) * plan.total_samples
+        n_blocks = int(sum(-(-int(f) * H // 128) * 4 for f in lengths))
+        exec_flop = split_executed_flop_per_block(L, args.layer_kernel) * n_blocks
+        achieved_gbs = bytes_launch / layer_avg_s / 1e9
+        roofline = {
+            "kernel": f"residual layer ({args.layer_kernel} persistent kernel, one fused WaveNet residual block)",
+            "bound": "hbm",
+            "achieved": round(achieved_gbs, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "algorithmic_bytes_per_launch": int(bytes_launch),
+            "avg_launch_ms": round(layer_avg_s * 1e3, 4),
+            "launches_timed": layer_n,
+            "mfma": {
+                "executed_f16_flop_per_launch": int(exec_flop),
+                "achieved_tflops": round(exec_flop / layer_avg_s / 1e12, 1),
+                "peak_tflops": F16_MFMA_PEAK_TFLOPS,
+                "frac": round(exec_flop / layer_avg_s / 1e12 / F16_MFMA_PEAK_TFLOPS, 4),
+            },
+            # the reference formulation's fp32 FLOPs per launch over the same time
+            "reference_flop_per_launch": int(flops_launch),
+            "reference_tflops": round(achieved_tflops, 1),
+            "hbm_GBs_measured": traffic and round(traffic / layer_avg_s / 1e9, 1),
+            # shader clock and matrix-pipe busy of the middle-layer launches (in-run PMC pass): the
+            # layer runs power-limited well under the 2.4 GHz max clock (DESIGN.md 3.0)
+            "clock_pmc": live_traffic[2],
+        }
+    else:
+        roofline = {
+            "kernel": f"residual layer ({args.layer_kernel} kernel, one fused WaveNet residual block)",
+            "bound": "mfma",
+            "achieved": round(achieved_tflops, 3),
+            "peak": FP32_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": round(achieved_tflops / FP32_PEAK_TFLOPS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "flop_per_launch": int(flops_launch),
+            "algorithmic_bytes_per_launch": int(layer_bytes_per_sample(params) * plan.total_samples),
+            "avg_launch_ms": round(layer_avg_s * 1e3, 4),
+            "launches_timed": layer_n,
+            # FLOPs the MFMAs actually execute (rocprofv3 SQ_INSTS_MFMA x 4096 per 32x32x2 f32 MFMA):
+            # below the reference count because the aux 1x1 runs at frame rate (DESIGN.md)
+            "executed_flop_per_launch": mfma_insts and int(mfma_insts * 4096),
+            "executed_frac": mfma_insts and round(mfma_insts * 4096 / layer_avg_s / 1e12 / FP32_PEAK_TFLOPS, 4),
+            "hbm_GBs": traffic and round(traffic / layer_avg_s / 1e9, 1),
+        }
+    return roofline
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-launch kernel times and "
+                         "roofline (rocprofv3 --pmc traffic passes), exact-fp32 leg, PCIe-inclusive rate, "
+                         "embedded vocoder runs, latency rows, CPU baseline (the options below that skip or "
+                         "size these legs apply with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's output of the last timed step as DIR/audio.npy "
+                         "(float32; a fixed seeded sample when larger than the dump budget)")
     ap.add_argument("--config", default="libritts_v1",
                     choices=["libritts_v1", "ljspeech_v1", "yesno_debug"] + VOCODERS)
     ap.add_argument("--utts", type=int, default=32, help="utterances per GPU per step (weak scaling)")
@@ -952,11 +1098,13 @@ def main():
         return pmc_child(args)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
-    # measured HBM traffic of the dominant kernel, before this process touches the GPU
+    # --full: measured HBM traffic of the dominant kernel, before this process touches the GPU
     live_traffic = (None, "off", None)
-    single = args.pmc == "auto" and int(os.environ.get("WORLD_SIZE", "1")) == 1
+    single = args.full and args.pmc == "auto" and int(os.environ.get("WORLD_SIZE", "1")) == 1
     if (single and args.config not in VOCODERS
             and not args.strong and args.sub_plans == 1 and args.layer_kernel in (None, "split16")
             and not args.no_fuse_first and not args.waves_per_wg and not args.wg_per_cu):
@@ -964,8 +1112,8 @@ def main():
     voc_traffic = (None, "off", None, None)
     if single and args.config in VOCODERS:
         voc_traffic = measure_program_traffic(args)
-    embed = (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config not in VOCODERS and not args.strong
-             and not args.no_vocoders and args.sub_plans == 1)
+    embed = (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.config not in VOCODERS
+             and not args.strong and not args.no_vocoders and args.sub_plans == 1)
     embed_traffic = {}
     if embed:
         for vc in EMBED_VOCODERS:
@@ -1063,13 +1211,14 @@ def main():
         run_step()
     torch.cuda.synchronize(dev)
 
-    # untimed pass with per-launch timing on: its events return to the engine's pool, so the timed
-    # steps record pooled events instead of creating them on the host between launches
-    eng.set_timing(True)
-    for _ in range(args.steps):
-        run_step()
-    torch.cuda.synchronize(dev)
-    eng.collect_timing()  # clear
+    if args.full:
+        # untimed pass with per-launch timing on: its events return to the engine's pool, so the timed
+        # steps record pooled events instead of creating them on the host between launches
+        eng.set_timing(True)
+        for _ in range(args.steps):
+            run_step()
+        torch.cuda.synchronize(dev)
+        eng.collect_timing()  # clear
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -1080,36 +1229,23 @@ def main():
     if world > 1:
         dist.barrier()
     local_elapsed = time.perf_counter() - t0
-    eng.set_timing(False)
-    timing = eng.collect_timing()
+    timing = None
+    if args.full:
+        eng.set_timing(False)
+        timing = eng.collect_timing()
     elapsed = max_over_ranks(local_elapsed, dev)
     # the split-f16 range flag of the last timed run (pwg_run_status; raises on a flagged run)
     if args.layer_kernel in ("split", "split16"):
         eng.run_status(plan)
     if not torch.isfinite(out).all():
         raise RuntimeError("non-finite generator output")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"audio": out})
     exact = None
-    if (world == 1 and not args.no_exact and not args.strong and subs is None
+    if (args.full and world == 1 and not args.no_exact and not args.strong and subs is None
             and args.layer_kernel in ("split", "split16")):
         exact = exact_fp32_leg(eng, plan, mel, noise, out, params, max(2, min(args.steps, 5)))
-
-    # PCIe-inclusive rate (never `value`): host mel + noise in pinned memory -> H2D -> forward ->
-    # D2H of the audio, like inference() called on host arrays (models/parallel_wavegan.py:244-263)
-    mel_h, noise_h = mel.cpu().pin_memory(), noise.cpu().pin_memory()
-    out_h = torch.empty(out.numel(), dtype=torch.float32).pin_memory()
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        mel.copy_(mel_h, non_blocking=True)
-        noise.copy_(noise_h, non_blocking=True)
-        eng.run(plan, mel, noise, out, check=False)
-        out_h.copy_(out, non_blocking=True)
-    torch.cuda.synchronize(dev)
-    if world > 1:
-        dist.barrier()
-    e2e = max_over_ranks(time.perf_counter() - t0, dev)
+    e2e = pcie_inclusive_seconds(eng, plan, mel, noise, out, args.steps, world, dev) if args.full else None
 
     if args.strong:
         samples_per_step = int(all_lengths.sum()) * H
@@ -1117,79 +1253,7 @@ def main():
         samples_per_step = plan.total_samples * world
     value = samples_per_step * args.steps / elapsed
     per_gpu = value / world
-    layer_ms, layer_n = timing["residual_layer"]
-    layer_avg_s = layer_ms / 1e3 / max(layer_n, 1)
-    flops_launch = layer_flops_per_sample(params) * plan.total_samples
-    achieved_tflops = flops_launch / layer_avg_s / 1e12
-    traffic = mfma_insts = None
-    traffic_source = None
-    if live_traffic[0] is not None:
-        traffic, traffic_source = live_traffic[:2]
-    elif os.path.exists(args.traffic_json):
-        try:
-            tj = json.load(open(args.traffic_json))
-            if (tj.get("config") == args.config and tj.get("utts") == args.utts and not args.strong
-                    and tj.get("layer_kernel", "persistent") == args.layer_kernel):
-                traffic = tj.get("hbm_bytes_per_launch")
-                mfma_insts = tj.get("mfma_insts_per_launch")
-                traffic_source = (f"{os.path.relpath(args.traffic_json, REPO)} (rocprofv3 --pmc FETCH_SIZE x2 + "
-                                  f"WRITE_SIZE of this workload, {tj.get('source', 'committed profile')}; "
-                                  f"not measured in this run: {live_traffic[1]})")
-        except (OSError, ValueError):
-            traffic = None
-    L = params["layers"]
-    if args.layer_kernel in ("split", "split16"):
-        # HBM-bound: algorithmic bytes of the engine's layer per launch / launch time
-        bytes_launch = split_layer_bytes_per_sample(params, H, L, fuse_first) * plan.total_samples
-        n_blocks = int(sum(-(-int(f) * H // 128) * 4 for f in lengths))
-        exec_flop = split_executed_flop_per_block(L, args.layer_kernel) * n_blocks
-        achieved_gbs = bytes_launch / layer_avg_s / 1e9
-        roofline = {
-            "kernel": f"residual layer ({args.layer_kernel} persistent kernel, one fused WaveNet residual block)",
-            "bound": "hbm",
-            "achieved": round(achieved_gbs, 1),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
-            "traffic": traffic,
-            "traffic_source": traffic_source,
-            "algorithmic_bytes_per_launch": int(bytes_launch),
-            "avg_launch_ms": round(layer_avg_s * 1e3, 4),
-            "launches_timed": layer_n,
-            "mfma": {
-                "executed_f16_flop_per_launch": int(exec_flop),
-                "achieved_tflops": round(exec_flop / layer_avg_s / 1e12, 1),
-                "peak_tflops": F16_MFMA_PEAK_TFLOPS,
-                "frac": round(exec_flop / layer_avg_s / 1e12 / F16_MFMA_PEAK_TFLOPS, 4),
-            },
-            # the reference formulation's fp32 FLOPs per launch over the same time
-            "reference_flop_per_launch": int(flops_launch),
-            "reference_tflops": round(achieved_tflops, 1),
-            "hbm_GBs_measured": traffic and round(traffic / layer_avg_s / 1e9, 1),
-            # shader clock and matrix-pipe busy of the middle-layer launches (in-run PMC pass): the
-            # layer runs power-limited well under the 2.4 GHz max clock
-            "clock_pmc": live_traffic[2],
-        }
-    else:
-        roofline = {
-            "kernel": f"residual layer ({args.layer_kernel} kernel, one fused WaveNet residual block)",
-            "bound": "mfma",
-            "achieved": round(achieved_tflops, 3),
-            "peak": FP32_PEAK_TFLOPS,
-            "unit": "TFLOP/s",
-            "frac": round(achieved_tflops / FP32_PEAK_TFLOPS, 4),
-            "traffic": traffic,
-            "traffic_source": traffic_source,
-            "flop_per_launch": int(flops_launch),
-            "algorithmic_bytes_per_launch": int(layer_bytes_per_sample(params) * plan.total_samples),
-            "avg_launch_ms": round(layer_avg_s * 1e3, 4),
-            "launches_timed": layer_n,
-            # FLOPs the MFMAs actually execute (rocprofv3 SQ_INSTS_MFMA x 4096 per 32x32x2 f32 MFMA):
-            # below the reference count because the aux 1x1 runs at frame rate
-            "executed_flop_per_launch": mfma_insts and int(mfma_insts * 4096),
-            "executed_frac": mfma_insts and round(mfma_insts * 4096 / layer_avg_s / 1e12 / FP32_PEAK_TFLOPS, 4),
-            "hbm_GBs": traffic and round(traffic / layer_avg_s / 1e9, 1),
-        }
+    roofline = layer_roofline(args, params, plan, lengths, timing, live_traffic, fuse_first) if args.full else None
     # per-rank wall time of the timed steps next to the max (load imbalance of the partition)
     rank_seconds = per_rank_seconds(local_elapsed, world, dev)
 
@@ -1198,10 +1262,10 @@ def main():
         return
 
     cpu = None
-    if args.cpu_utts > 0 and world == 1:
+    if args.full and args.cpu_utts > 0 and world == 1:
         cpu = cpu_baseline(params, sd, args.config, args.cpu_utts, args.cpu_reps)
     lat = None
-    if not args.no_latency and world == 1:
+    if args.full and not args.no_latency and world == 1:
         lat = latency_rows(dev)
 
     parallelism = (f"utterance-sharded x{world} (no data-path collective; weights broadcast once: {broadcast})"
@@ -1236,18 +1300,21 @@ def main():
         "value_per_gpu": round(per_gpu, 1),
         "x_realtime_per_gpu": round(per_gpu / fs, 1),
         "rtf_per_gpu": per_gpu and fs / per_gpu,
-        "kernel_ms_per_step": {k: round(ms / args.steps, 3) for k, (ms, _) in timing.items()},
         "range_check": "ok (pwg_run_status after the timed steps)" if args.layer_kernel in ("split", "split16")
                        else "n/a (exact fp32)",
-        "roofline": roofline,
         "model_flop_per_sample": round(model_flops_per_sample(params), 1),
         "model_tflops": round(value / world * model_flops_per_sample(params) / 1e12, 3),
-        "pcie_inclusive_value": round(samples_per_step * args.steps / e2e, 1),
-        "cpu_baseline": cpu,
-        "latency": lat,
     }
     res["rank_seconds"] = [round(x, 4) for x in rank_seconds]
-    res["exact_fp32"] = exact
+    if args.full:
+        res.update({
+            "kernel_ms_per_step": {k: round(ms / args.steps, 3) for k, (ms, _) in timing.items()},
+            "roofline": roofline,
+            "pcie_inclusive_value": round(samples_per_step * args.steps / e2e, 1),
+            "cpu_baseline": cpu,
+            "latency": lat,
+            "exact_fp32": exact,
+        })
     if embed:
         vocs = {}
         for vc in EMBED_VOCODERS:

@@ -93,17 +93,18 @@ def test_rccl_broadcast_capi(built_lib, cuda_device):
     assert torch.equal(y, eng.infer([mel], [noise])[0])
 
 
-def test_bench_self_launches_ranks(built_lib, cuda_device):
+def test_bench_self_launches_ranks(built_lib, cuda_device, tmp_path):
     """`bench.py --gpus 2` as ONE command starts its two ranks itself (a torch.distributed.run
     child); on this 1-GPU box they share cuda:0 over gloo. The line reports 2 ranks, 1 device and
-    both ranks' seconds."""
+    both ranks' seconds; being a plain run it carries no --full leg, and --dump-outputs leaves
+    rank 0's audio of the last timed step."""
     import json
 
     env = dict(os.environ, PWG_NO_BUILD="1", PWG_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--utts", "8", "--no-latency", "--cpu-seconds", "0", "--pmc", "off"]
+           "--utts", "8", "--no-latency", "--cpu-seconds", "0", "--pmc", "off", "--dump-outputs", str(tmp_path)]
     res = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=110)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -113,3 +114,8 @@ def test_bench_self_launches_ranks(built_lib, cuda_device):
     assert len(line["rank_seconds"]) == 2 and all(t > 0 for t in line["rank_seconds"])
     assert line["config"]["global_batch"] == 16
     assert line["value"] > 0
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    assert not {"roofline", "kernel_ms_per_step", "cpu_baseline", "latency", "exact_fp32", "vocoders"} & set(line)
+    audio = np.load(os.path.join(tmp_path, "audio.npy"))
+    assert audio.dtype == np.float32 and audio.shape == (line["config"]["samples_per_step_per_gpu"],)
+    assert np.isfinite(audio).all() and np.abs(audio).max() > 0

@@ -47,6 +47,26 @@ def test_bench_launch_command_form():
     assert cmd[-5] == os.path.join(REPO, "bench.py")
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an array within the budget is written whole as float32; a larger one as the
+    same seeded sample of its elements on every call."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    x = torch.arange(1000, dtype=torch.float32) * 0.5
+    bench.dump_outputs(str(tmp_path / "a"), {"audio": x})
+    got = np.load(tmp_path / "a" / "audio.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 300)
+    bench.dump_outputs(str(tmp_path / "b"), {"audio": x})
+    bench.dump_outputs(str(tmp_path / "c"), {"audio": x})
+    b, c = np.load(tmp_path / "b" / "audio.npy"), np.load(tmp_path / "c" / "audio.npy")
+    assert b.dtype == np.float32 and 0 < b.size <= 300 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.all(np.isin(b, x.numpy()))
+
+
 def test_bench_refuses_more_ranks_than_gpus_on_nccl():
     """`bench.py --gpus 2` as one process on the nccl backend with fewer than 2 visible GPUs
     (none here) exits non-zero before touching a GPU instead of timing one process."""

@@ -52,5 +52,5 @@ def infer(self, mels, mean=None, scale=None):
 cnet.CnetEngine.infer = infer
 import bench  # noqa: E402
 
-sys.argv = ["bench.py"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full"] + sys.argv[1:]
 bench.main()

@@ -15,6 +15,6 @@ import json, sys
 for r in json.load(open(sys.argv[1]))["rows"]:
     print(sys.argv[2], r["frames"], r["batch"], "median_ms", r["median_ms"], "kernel_ms", r["kernel_ms"], "samples/s", r["samples_per_s"])
 PY
-  PWG_LIB_PATH=$lib timeout -k 10 300 python bench.py --cpu-seconds 0 --no-latency --steps 5 --warmup 2 > "$OUT/bench_$v.json"
+  PWG_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --cpu-seconds 0 --no-latency --steps 5 --warmup 2 > "$OUT/bench_$v.json"
   python -c "import json; d=json.load(open('$OUT/bench_$v.json')); print('$v bench', d['value'], d['roofline']['avg_launch_ms'], d['kernel_ms_per_step'])"
 done

@@ -3,8 +3,8 @@
 # Usage: bash tools/gpu_run.sh OUT STEP [STEP ...]
 #   tests[:EXPR]   pytest -m gpu (optionally -k EXPR), stops the pass on failure
 #   smoke          __graft_entry__.smoke()
-#   bench[:ARGS]   python bench.py ARGS (comma-separated, e.g. bench:--steps,3,--no-latency)
-#   voc:CFG        python bench.py --config CFG
+#   bench[:ARGS]   python bench.py ARGS (comma-separated, e.g. bench:--full,--steps,3,--no-latency)
+#   voc:CFG        python bench.py --full --config CFG
 #   prof[:ARGS]    rocprofv3 --kernel-trace --stats over bench.py ARGS
 # Every GPU step has its own time limit; the first failure ends the pass.
 set -e
@@ -27,7 +27,7 @@ for step in "$@"; do
       timeout -k 10 600 python bench.py ${arg//,/ } > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     voc)
-      timeout -k 10 400 python bench.py --config "$arg" > "$OUT/$arg.json" 2> "$OUT/$arg.err" || { tail -30 "$OUT/$arg.err"; exit 1; }
+      timeout -k 10 400 python bench.py --full --config "$arg" > "$OUT/$arg.json" 2> "$OUT/$arg.err" || { tail -30 "$OUT/$arg.err"; exit 1; }
       cat "$OUT/$arg.json" ;;
     prof)
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$OUT/prof" -o run --output-format csv \
