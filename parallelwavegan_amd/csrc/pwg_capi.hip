@@ -1074,6 +1074,7 @@ static int pwg_run_impl(PwgPlan* p, const float* packed, const float* mel, const
     da.n = std::min(PLAN_CHUNK, p->n_utts - u0);
     da.u0 = u0;
     da.gap_tiles = (int)(h->gap / TILE);
+    da.H = (int)h->aux.H;
     for (int i = 0; i < da.n; ++i) da.utts[i] = p->utts[u0 + i];
     da.d_utts = d_utts; da.tile_utt = d_tile_utt; da.gap_col0 = d_gap_col0; da.blocks = d_blocks;
     // work-queue heads and the range flag (adjacent) start at zero every run

@@ -142,7 +142,7 @@ struct BlockDesc {
   int frame_base;  // its first frame in C1 / D
   int io_off;      // its first sample in the caller's noise/output arrays
   int utt;
-  int pad;
+  int f0;          // t0 / H: the frame of the block's first sample (spares the split16 body the division)
 };
 
 // Slim argument block of the persistent layer kernel (fewer live scalars than LayerArgs).
@@ -264,6 +264,7 @@ struct PlanDescArgs {
   int n;          // utterances in this chunk
   int u0;         // plan index of utts[0]
   int gap_tiles;  // zero tiles between segments (gap / TILE)
+  int H;          // samples per frame (BlockDesc::f0)
   UttDesc* d_utts;
   int* tile_utt;
   long long* gap_col0;

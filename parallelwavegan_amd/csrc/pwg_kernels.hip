@@ -1037,7 +1037,7 @@ __global__ void __launch_bounds__(256) pwg_plan_desc_kernel(const PlanDescArgs a
     b.frame_base = (int)d.frame_base;
     b.io_off = (int)d.io_off;
     b.utt = a.u0 + y;
-    b.pad = 0;
+    b.f0 = b.t0 / a.H;
     a.blocks[d.first_tile * (TILE / 32) + j] = b;
     if (a.prog != nullptr) a.prog[d.first_tile * (TILE / 32) + j] = 0;
     if ((j & (TILE / 32 - 1)) == 0) a.tile_utt[d.first_tile + j / (TILE / 32)] = a.u0 + y;

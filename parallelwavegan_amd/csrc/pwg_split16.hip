@@ -108,14 +108,35 @@ __device__ __forceinline__ Pair16 split_pair16(float v0, float v1) {
 
 }  // namespace
 
-// dword offset of piece q of column c (n-tile from c) for lane group g; pieces of one n-tile are
-// 256 dwords (1 KB) apart
-__device__ __forceinline__ size_t row16(int c, int g) {
-  return (size_t)(c >> 5) * 2048 + (size_t)((c >> 4) & 1) * 1024 + (size_t)g * 64 + (size_t)(c & 15) * 4;
+// Addressing. Piece q of column col for lane group g lies at byte
+//   (col >> 4) * 4096 + q * 1024 + g * 256 + (col & 15) * 16
+// of its plane (a 32-column tile is two 16-column n-tiles of 4 KB). A block's column base is
+// wave-uniform, so every access is a uniform 64-bit part (plane + 16-column tile, SALU) plus a
+// 32-bit byte offset per lane plus an immediate (the piece):
+//   * columns base + c with base a multiple of 16 (the center tap, taps shifted by a multiple of
+//     16, skip, the stores): the lane offset is the constant g * 256 + c * 16 = 16 * lane;
+//   * a tap shifted by r = base & 15 != 0: column r + c crosses into the next n-tile per lane,
+//     lane offset shifted16(r, g, c), computed once per tap.
+__device__ __forceinline__ unsigned shifted16(int r, int g, int c) {
+  const unsigned s = (unsigned)(r + c);  // < 32
+  return (unsigned)g * 256u + (s >> 4) * 4096u + (s & 15u) * 16u;
 }
 
-// byte offset of piece q of column c for lane group g (row16 in bytes)
-__device__ __forceinline__ unsigned row16_bytes(int c, int g) { return (unsigned)row16(c, g) * 4u; }
+// The fields of a block descriptor as wave-uniform values. The descriptor arrives through a vector
+// load (a block ahead), so without this every index and address derived from it is per-lane VALU
+// work, in 64 bits where it feeds an address.
+__device__ __forceinline__ BlockDesc uniform_desc(const BlockDesc& d) {
+  BlockDesc u;
+  u.col = __builtin_amdgcn_readfirstlane(d.col);
+  u.t0 = __builtin_amdgcn_readfirstlane(d.t0);
+  u.T = __builtin_amdgcn_readfirstlane(d.T);
+  u.frames = __builtin_amdgcn_readfirstlane(d.frames);
+  u.frame_base = __builtin_amdgcn_readfirstlane(d.frame_base);
+  u.io_off = __builtin_amdgcn_readfirstlane(d.io_off);
+  u.utt = __builtin_amdgcn_readfirstlane(d.utt);
+  u.f0 = __builtin_amdgcn_readfirstlane(d.f0);
+  return u;
+}
 
 // buffer resource over a wave-uniform base (num_records 2 GB: the pipelined path's planes are smaller)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc16(const void* base) {
@@ -126,12 +147,46 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc16(const void* base) {
 // sc1 (write-through / L1-bypassing) 16-byte accesses: the pipelined kernel's hand-off bytes
 // (cdna_hip_programming.md Guideline 16: every store and every load of a handed-off byte is sc1)
 constexpr int AUX_SC1 = 16;
-__device__ __forceinline__ u32x4 ld16_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, AUX_SC1));
-}
-__device__ __forceinline__ void st16_sc1(__amdgpu_buffer_rsrc_t r, unsigned off, u32x4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, AUX_SC1);
-}
+
+// A plane (x or skip) as a wave addresses it: byte `sb` (wave-uniform, 64-bit: a per-layer plan's
+// planes may exceed 2 GB) + `vo` (the lane's 32-bit offset) + `imm`. Per-layer launches: global
+// accesses; the compiler keeps plane + vo as a loop-invariant vector address and adds `sb` with
+// one 64-bit VALU add per group of pieces (it does not pick the SGPR-base form here; a block
+// keeps 12 such adds, from ~120 instructions of per-lane address work). PIPE: sc1 buffer
+// accesses with `sb` truncated to 32 bits as the SGPR offset. That holds because `sb` >= 0 (a tap
+// row starts inside the leading gap at the earliest) and because the host puts a plan on the
+// pipelined or the synchronised launch only when a whole plane, gaps included, stays below 2 GB
+// (pwg_capi.hip: pipe_ok at plan creation, use_sync in the run), which is also rsrc16's range.
+template <bool PIPE>
+struct Plane16 {
+  char* p;
+  __amdgpu_buffer_rsrc_t r;
+  __device__ __forceinline__ explicit Plane16(const void* base) : p(const_cast<char*>(static_cast<const char*>(base))) {
+    if constexpr (PIPE) r = rsrc16(base);
+  }
+  // The uniform part as an SGPR pair the compiler cannot fold into the lane's part (folded, the
+  // n-tiles' 4 KB step, too large for the immediate, costs a 64-bit vector add with carry per
+  // group). The constraint also makes a `sb` that is not provably uniform a compile error.
+  __device__ __forceinline__ char* at(long long sb) const {
+    asm("" : "+s"(sb));
+    return p + sb;
+  }
+  // NT: nontemporal (the skip plane's read-modify-write and the x stores of the per-layer path)
+  template <bool NT = false>
+  __device__ __forceinline__ u32x4 load(long long sb, unsigned vo, int imm) const {
+    if constexpr (PIPE) {
+      return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, vo + (unsigned)imm, (unsigned)sb, AUX_SC1));
+    } else {
+      const u32x4* q = reinterpret_cast<const u32x4*>(at(sb) + imm + (size_t)vo);
+      if constexpr (NT) return __builtin_nontemporal_load(q);
+      else return *q;
+    }
+  }
+  __device__ __forceinline__ void store(long long sb, unsigned vo, int imm, u32x4 v) const {
+    if constexpr (PIPE) __builtin_amdgcn_raw_buffer_store_b128(v, r, vo + (unsigned)imm, (unsigned)sb, AUX_SC1);
+    else __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(at(sb) + imm + (size_t)vo));
+  }
+};
 
 // LDS image of one layer (dwords): GEMM-1 A fragments [tap 3][ks 2][m 8][hi/lo 2][lane 64][4]
 // | GEMM-2 [ks 2][m 8][hi/lo 2][lane 64][4] | gate bias pairs [m 8][c 16] | sqrt(.5) b_out [g 4][16]
@@ -169,17 +224,22 @@ __device__ __forceinline__ void s16_stage(const SplitArgs& a, unsigned* smem16) 
 // PWG_OPT_FUSE_FIRST_CONV): first_conv (models/parallel_wavegan.py:81,161, x0 = w z + b, zero
 // outside the utterance) is evaluated from the 4-byte noise with the same fmaf and pair split as
 // pwg_first_conv_split16_kernel (bit-identical), so x0 never touches HBM. PIPE: sc1 loads.
-template <int TC, bool FIRST, bool PIPE, int NTN = 2>
+// `d` and h16 are wave-uniform (uniform_desc). AL: the layer's dilation is a multiple of 16, so
+// every tap's lane offset is the constant one (the center tap's always is).
+template <int TC, bool FIRST, bool PIPE, int NTN = 2, bool AL = false>
 __device__ __forceinline__ void s16_bload(const SplitArgs& a, const float* s_fwb, const BlockDesc& d, int tap,
                                           u32x4 (&b)[8], int g, int c, int h16 = 0) {
   if constexpr (FIRST) {
     const f32x4* fw4 = reinterpret_cast<const f32x4*>(s_fwb) + g;
     const f32x4* fb4 = reinterpret_cast<const f32x4*>(s_fwb + 64) + g;
+    const char* nz = reinterpret_cast<const char*>(a.noise + d.io_off);  // the utterance's noise
+    const int ts = d.t0 + h16 + (tap - TC) * a.dil;
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt) {
-      const int t = d.t0 + h16 + 16 * nt + c + (tap - TC) * a.dil;
+      const int t = ts + 16 * nt + c;
       const bool inside = t >= 0 && t < d.T;
-      const float z = a.noise[d.io_off + (t < 0 ? 0 : (t >= d.T ? d.T - 1 : t))];
+      const unsigned tcl = (unsigned)(t < 0 ? 0 : (t >= d.T ? d.T - 1 : t));
+      const float z = *reinterpret_cast<const float*>(nz + (size_t)(tcl * 4u));
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         float v[8];
@@ -192,36 +252,30 @@ __device__ __forceinline__ void s16_bload(const SplitArgs& a, const float* s_fwb
         split8x<0>(v, b[nt * 4 + ks * 2], b[nt * 4 + ks * 2 + 1]);
       }
     }
-  } else if constexpr (PIPE) {
-    const __amdgpu_buffer_rsrc_t r = rsrc16(a.x_in);
-    const int cc = d.col + h16 + (tap - TC) * a.dil;
-#pragma unroll
-    for (int nt = 0; nt < NTN; ++nt) {
-      const unsigned off = row16_bytes(cc + 16 * nt + c, g);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) b[nt * 4 + q] = ld16_sc1(r, off + q * 1024u);
-    }
   } else {
-    const int cc = d.col + h16 + (tap - TC) * a.dil;
+    const int cc = d.col + h16 + (tap - TC) * a.dil;  // first column of the tap row (>= 0: the gaps)
+    const long long sb = (long long)(cc >> 4) * 4096;
+    const unsigned vo = (AL || tap == TC) ? 16u * (unsigned)(16 * g + c) : shifted16(cc & 15, g, c);
+    const Plane16<PIPE> x(a.x_in);
 #pragma unroll
-    for (int nt = 0; nt < NTN; ++nt) {
-      const u32x4* p = reinterpret_cast<const u32x4*>(a.x_in + row16(cc + 16 * nt + c, g));
+    for (int nt = 0; nt < NTN; ++nt)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) b[nt * 4 + q] = p[q * 64];
-    }
+      for (int q = 0; q < 4; ++q) b[nt * 4 + q] = x.load(sb + nt * 4096, vo, q * 1024);
   }
 }
 
 // D rows of a block's aux window: lane group g covers window frames fw0 + 2g, fw0 + 2g + 1 of the
 // frame-rate aux projection, in the split16 layout [c 16][m 8] (pwg_aux_proj_kernel, split == 2).
+// `bd` is wave-uniform.
 __device__ __forceinline__ void s16_load_dv(const SplitArgs& a, const BlockDesc& bd, unsigned (&dv)[2][8], int g,
                                             int c) {
-  const int fw0 = bd.t0 / a.H - a.J1;
+  const int fw0 = bd.f0 - a.J1;
+  const char* dbase = reinterpret_cast<const char*>(a.d + (size_t)bd.frame_base * 128);  // the utterance's D rows
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int f = fw0 + 2 * g + j;
     const int fc = f < 0 ? 0 : (f >= bd.frames ? bd.frames - 1 : f);  // weight 0 there
-    const u32x4* drow = reinterpret_cast<const u32x4*>(a.d + (size_t)(bd.frame_base + fc) * 128 + 8 * c);
+    const u32x4* drow = reinterpret_cast<const u32x4*>(dbase + (size_t)((unsigned)fc * 512u + (unsigned)c * 32u));
     const u32x4 d0 = drow[0], d1 = drow[1];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -236,20 +290,15 @@ __device__ __forceinline__ void s16_load_dv(const SplitArgs& a, const BlockDesc&
 template <bool PIPE, int NTN = 2>
 __device__ __forceinline__ void s16_load_skip(const SplitArgs& a, const BlockDesc& bd, f32x4 (&sk)[4][2], int g,
                                               int c, int h16 = 0) {
-  [[maybe_unused]] __amdgpu_buffer_rsrc_t rs;
-  if constexpr (PIPE) rs = rsrc16(a.skip);
+  const Plane16<PIPE> skip(a.skip);
+  const long long sb = (long long)((bd.col + h16) >> 4) * 4096;
+  const unsigned vo = 16u * (unsigned)(16 * g + c);
 #pragma unroll
   for (int nt = 0; nt < NTN; ++nt)
 #pragma unroll
     for (int ms = 0; ms < 4; ++ms) {
-      if (a.first) {
-        sk[ms][nt] = reinterpret_cast<const f32x4*>(a.skip0 + 16 * g)[ms];
-      } else if constexpr (PIPE) {
-        sk[ms][nt] = __builtin_bit_cast(f32x4, ld16_sc1(rs, row16_bytes(bd.col + h16 + 16 * nt + c, g) + ms * 1024u));
-      } else {
-        const f32x4* sp = reinterpret_cast<const f32x4*>(a.skip + row16(bd.col + h16 + 16 * nt + c, g));
-        sk[ms][nt] = __builtin_nontemporal_load(sp + ms * 64);
-      }
+      if (a.first) sk[ms][nt] = reinterpret_cast<const f32x4*>(a.skip0 + 16 * g)[ms];
+      else sk[ms][nt] = __builtin_bit_cast(f32x4, skip.template load<true>(sb + nt * 4096, vo, ms * 1024));
     }
 }
 
@@ -266,12 +315,17 @@ __device__ __forceinline__ void s16_load_skip(const SplitArgs& a, const BlockDes
 // block's first frame: bit-identical per column.
 // poison (LAST): the run's earlier layers did not complete (a PWG_STATUS_REDO bit was set when the
 // launch started), so the block writes NaN audio instead of a plausible-looking wrong result.
-template <bool LAST, int TC, bool FIRST, bool PIPE, int NTN = 2, typename Mid>
-__device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* smem16, const BlockDesc& bd,
-                                          const BlockDesc& bdn, bool has_next, u32x4 (&b0)[8], u32x4 (&b1)[8],
-                                          bool& nonfinite, Mid&& mid, int h16 = 0, int h16n = 0,
+// bd_v, bdn_v, h16_v, h16n_v: as loaded (per-lane registers holding wave-uniform values); the body
+// works on their scalar copies, so its index math is SALU and its addresses are a uniform base
+// plus a 32-bit lane offset. AL: as s16_bload.
+template <bool LAST, int TC, bool FIRST, bool PIPE, int NTN = 2, bool AL = false, typename Mid>
+__device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* smem16, const BlockDesc& bd_v,
+                                          const BlockDesc& bdn_v, bool has_next, u32x4 (&b0)[8], u32x4 (&b1)[8],
+                                          bool& nonfinite, Mid&& mid, int h16_v = 0, int h16n_v = 0,
                                           bool poison = false) {
   static_assert(NTN == 2 || !LAST, "half blocks: middle layers");
+  const BlockDesc bd = uniform_desc(bd_v);
+  const int h16 = NTN == 1 ? __builtin_amdgcn_readfirstlane(h16_v) : 0;
   const unsigned* s_wg = smem16;
   const unsigned* s_w2 = s_wg + Split16Smem::WG;
   const unsigned* s_bg = s_w2 + Split16Smem::W2;
@@ -288,22 +342,39 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
   // group 0 only); bw = the composite upsampler weights of the lane's two window frames
   unsigned dv[2][8];  // [frame][m], loaded during GEMM 1
   float bw[2][2];  // [nt][frame]
+  // Position of the lane's sample in the frame grid: shift = t / H - t0 / H and rem = t % H. With
+  // H >= 32 a block spans at most two frames, so from the block's own remainder (t0 - f0 H, SALU)
+  // they are one add and a compare-select; smaller hops divide (uniform choice). A dead lane
+  // (t >= T) only needs an in-range table row: its weight is 0.
+  const bool two_frames = a.H >= 32;
+  const int rem0 = bd.t0 - bd.f0 * a.H;
 #pragma unroll
   for (int nt = 0; nt < NTN; ++nt) {
-    const int t = bd.t0 + h16 + 16 * nt + c;
+    const int x = h16 + 16 * nt + c;
+    const int t = bd.t0 + x;
     const bool live = t < bd.T;
     const int tc = live ? t : bd.T - 1;
+    int shift, rem;
+    if (two_frames) {
+      const int r = rem0 + x;
+      const bool wrap = r >= a.H;
+      shift = wrap ? 1 : 0;
+      rem = wrap ? r - a.H : r;
+    } else {
+      shift = t / a.H - bd.t0 / a.H;
+      rem = tc % a.H;
+    }
     int roff;
     if (bd.frames < a.Fmin) roff = a.tab_small + (a.H * bd.frames * (bd.frames - 1) / 2 + tc) * AUX_J4;
     else if (tc < a.TL) roff = a.tab_left + tc * AUX_J4;
     else if (tc >= bd.T - a.TR) roff = a.tab_right + (bd.T - 1 - tc) * AUX_J4;
-    else roff = (tc % a.H) * AUX_J4;
-    const int shift = t / a.H - bd.t0 / a.H;
+    else roff = rem * AUX_J4;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int idx = 2 * g + j - shift;
       const bool ok = live && idx >= 0 && idx < AUX_J4;
-      const float w = a.tab[roff + (idx < 0 ? 0 : (idx >= AUX_J4 ? AUX_J4 - 1 : idx))];
+      const unsigned e = (unsigned)(roff + (idx < 0 ? 0 : (idx >= AUX_J4 ? AUX_J4 - 1 : idx)));
+      const float w = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.tab) + (size_t)(e * 4u));
       bw[nt][j] = ok ? w : 0.f;
     }
   }
@@ -341,10 +412,10 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt) acc[m][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 acc2[8][2];
-  s16_bload<TC, FIRST, PIPE, NTN>(a, s_fwb, bd, T1, b1, g, c, h16);
+  s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bd, T1, b1, g, c, h16);
   mma_tap(acc, b0, 0);
   s16_load_dv(a, bd, dv, g, c);
-  s16_bload<TC, FIRST, PIPE, NTN>(a, s_fwb, bd, TC, b0, g, c, h16);
+  s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bd, TC, b0, g, c, h16);
   mma_tap(acc, b1, T1);
   mma_tap(acc, b0, TC);
   if (!LAST) {
@@ -412,7 +483,11 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
   // GEMM 2, its rows are still in L2 (round 4 per-layer PMC: loading it during the center tap's
   // MFMAs, ~0.7 unit-times earlier, re-read 1.30-1.38x the algorithmic bytes from HBM, here
   // 1.02-1.13x; tools/diag/layer_fetch.sh)
-  if (has_next) s16_bload<TC, FIRST, PIPE, NTN>(a, s_fwb, bdn, 0, b0, g, c, h16n);
+  if (has_next) {
+    const BlockDesc bdn = uniform_desc(bdn_v);
+    const int h16n = NTN == 1 ? __builtin_amdgcn_readfirstlane(h16n_v) : 0;
+    s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bdn, 0, b0, g, c, h16n);
+  }
   // ---- GEMM 2: [skip; out] rows, 8 m-tiles (last layer: the 4 skip tiles)
   constexpr int M2 = LAST ? 4 : 8;
   const u32x4* w2l = reinterpret_cast<const u32x4*>(s_w2) + lane;
@@ -439,22 +514,15 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
     }
 
   if (!LAST) {
-    [[maybe_unused]] __amdgpu_buffer_rsrc_t rsk, rx;
-    if constexpr (PIPE) {
-      rsk = rsrc16(a.skip);
-      rx = rsrc16(a.x_out);
-    }
+    const Plane16<PIPE> skip(a.skip), xo(a.x_out);
+    const long long sb = (long long)((bd.col + h16) >> 4) * 4096;
+    const unsigned vo = 16u * (unsigned)lane;
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt) {
-      const int col = bd.col + h16 + 16 * nt + c;
       const bool live = bd.t0 + h16 + 16 * nt + c < bd.T;
 #pragma unroll
-      for (int ms = 0; ms < 4; ++ms) {
-        if constexpr (PIPE)
-          st16_sc1(rsk, row16_bytes(col, g) + ms * 1024u, __builtin_bit_cast(u32x4, acc2[ms][nt]));
-        else
-          __builtin_nontemporal_store(acc2[ms][nt], reinterpret_cast<f32x4*>(a.skip + row16(col, g)) + ms * 64);
-      }
+      for (int ms = 0; ms < 4; ++ms)
+        skip.store(sb + nt * 4096, vo, ms * 1024, __builtin_bit_cast(u32x4, acc2[ms][nt]));
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
         float v[8];
@@ -469,14 +537,8 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
             vl[k] = live ? vl[k] : 0u;
           }
         }
-        if constexpr (PIPE) {
-          st16_sc1(rx, row16_bytes(col, g) + (ks * 2) * 1024u, vh);
-          st16_sc1(rx, row16_bytes(col, g) + (ks * 2 + 1) * 1024u, vl);
-        } else {
-          u32x4* xp = reinterpret_cast<u32x4*>(a.x_out + row16(col, g));
-          __builtin_nontemporal_store(vh, xp + (ks * 2) * 64);
-          __builtin_nontemporal_store(vl, xp + (ks * 2 + 1) * 64);
-        }
+        xo.store(sb + nt * 4096, vo, (ks * 2) * 1024, vh);
+        xo.store(sb + nt * 4096, vo, (ks * 2 + 1) * 1024, vl);
       }
     }
   } else {
@@ -567,7 +629,10 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
 // NTN = 1 (small plans, the B = 1 latency path): the work unit is half a block (one 16-column
 // n-tile; unit u = block u / 2, columns 16 (u % 2) + [0, 16)), so twice the waves share a layer and
 // each wave's dependent chain runs half the MFMAs; bit-identical to whole blocks.
-template <bool LAST, int TC, bool FIRST, int NTN = 2>
+// AL: the layer's dilation is a multiple of 16 (s16_bload; the host knows it). NTN stays the last
+// template argument: bench.py tells the kernels apart by their names, where a name ending in
+// ", true>" does not count as a middle layer.
+template <bool LAST, int TC, bool FIRST, bool AL, int NTN>
 __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitArgs a) {
   constexpr int UB = NTN == 1 ? 1 : 0;  // log2(units per block)
   const int n_units = a.n_blocks << UB;
@@ -599,7 +664,9 @@ __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitAr
   if (has0) {
     bdn = a.blocks[blk0 >> UB];
     h16n = NTN == 1 ? 16 * (blk0 & 1) : 0;
-    if constexpr (!FIRST) s16_bload<TC, false, false, NTN>(a, nullptr, bdn, 0, b0, lane >> 4, lane & 15, h16n);
+    if constexpr (!FIRST)
+      s16_bload<TC, false, false, NTN, AL>(a, nullptr, uniform_desc(bdn), 0, b0, lane >> 4, lane & 15,
+                                           NTN == 1 ? __builtin_amdgcn_readfirstlane(h16n) : 0);
   }
   s16_stage<LAST, FIRST>(a, smem16);
   __syncthreads();
@@ -653,7 +720,9 @@ __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitAr
     return;
   }
   const float* s_fwb = reinterpret_cast<const float*>(smem16 + Split16Smem::dwords(LAST));
-  if constexpr (FIRST) s16_bload<TC, true, false, NTN>(a, s_fwb, bdn, 0, b0, lane >> 4, lane & 15, h16n);
+  if constexpr (FIRST)
+    s16_bload<TC, true, false, NTN>(a, s_fwb, uniform_desc(bdn), 0, b0, lane >> 4, lane & 15,
+                                    NTN == 1 ? __builtin_amdgcn_readfirstlane(h16n) : 0);
   bool nonfinite = false;  // LAST: range flag (pwg_run_status)
   while (true) {
     const BlockDesc bd = bdn;
@@ -662,7 +731,7 @@ __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitAr
     bdn = a.blocks[pf >> UB];
     h16n = NTN == 1 ? 16 * (pf & 1) : 0;
     int ticket = 0;
-    s16_block<LAST, TC, FIRST, false, NTN>(a, smem16, bd, bdn, true, b0, b1, nonfinite, [&]() {
+    s16_block<LAST, TC, FIRST, false, NTN, AL>(a, smem16, bd, bdn, true, b0, b1, nonfinite, [&]() {
       if (nblk >= 0) ticket = ticket_issue();
     }, h16, h16n, poison);
     if (tr && n_done++ == 0) t_first = __builtin_amdgcn_s_memrealtime();
@@ -739,7 +808,7 @@ __device__ __forceinline__ void pipe_layer(const PipeArgs& p, int l, unsigned* s
   while (blk < a.n_blocks) {
     const BlockDesc bd = a.blocks[blk];
     wait_deps(blk);
-    s16_bload<TC, FIRST, true>(a, s_fwb, bd, 0, b0, lane >> 4, lane & 15);
+    s16_bload<TC, FIRST, true>(a, s_fwb, uniform_desc(bd), 0, b0, lane >> 4, lane & 15);
     int next = 0;
     s16_block<LAST, TC, FIRST, true>(a, smem16, bd, bd, false, b0, b1, nonfinite, [&]() { next = ticket(); });
     if (!LAST) {
@@ -794,7 +863,7 @@ __device__ __forceinline__ void sync_layer(const SplitArgs& a, const unsigned* s
   constexpr int UB = NTN == 1 ? 1 : 0;
   const int n_units = a.n_blocks << UB;
   const int nw = a.compute_waves;
-  const int wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // unit indices and descriptors: scalar
   if (wave >= nw) return;
   const int lane = threadIdx.x & 63;
   const int xcd = blockIdx.x & 7;
@@ -807,7 +876,8 @@ __device__ __forceinline__ void sync_layer(const SplitArgs& a, const unsigned* s
   BlockDesc bd = a.blocks[u >> UB];
   int h16 = NTN == 1 ? 16 * (u & 1) : 0;
   u32x4 b0[8], b1[8];
-  s16_bload<TC, FIRST, true, NTN>(a, s_fwb, bd, 0, b0, lane >> 4, lane & 15, h16);
+  s16_bload<TC, FIRST, true, NTN>(a, s_fwb, uniform_desc(bd), 0, b0, lane >> 4, lane & 15,
+                                  NTN == 1 ? __builtin_amdgcn_readfirstlane(h16) : 0);
   while (true) {
     const int un = u + x_waves;
     const bool has_next = un < x_end;
@@ -964,10 +1034,10 @@ hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, i
   if (a.compute_waves < 1 || a.compute_waves > waves_per_wg) return hipErrorInvalidValue;
   if (half && last) return hipErrorInvalidValue;  // the head needs both n-tiles of a block
   const dim3 grid((unsigned)n_wg), block((unsigned)(64 * waves_per_wg));
-#define PWG_SPLIT16_LAUNCH(LAST_, TC_, FIRST_, NTN_)                                                    \
+#define PWG_SPLIT16_LAUNCH(LAST_, TC_, FIRST_, NTN_, AL_)                                               \
   {                                                                                                     \
     const size_t lds = sizeof(unsigned) * (Split16Smem::dwords(LAST_) + (FIRST_ ? 128 : 0));            \
-    auto kfn = &pwg_layer_split16_kernel<LAST_, TC_, FIRST_, NTN_>;                                     \
+    auto kfn = &pwg_layer_split16_kernel<LAST_, TC_, FIRST_, AL_, NTN_>;                                \
     hipError_t e_ = allow_lds(reinterpret_cast<const void*>(kfn), (int)lds);                           \
     if (e_ != hipSuccess) return e_;                                                                    \
     hipLaunchKernelGGL(kfn, grid, block, lds, s, a);                                                    \
@@ -975,19 +1045,24 @@ hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, i
   }
   const bool first = a.noise != nullptr;  // fused first_conv (never together with last: L > 1)
   if (first && last) return hipErrorInvalidValue;
+  // middle layers: taps shifted by a multiple of 16 columns keep the constant lane offset
+  const bool al = a.dil % 16 == 0;
+#define PWG_SPLIT16_MIDDLE(TC_, NTN_) \
+  { if (al) PWG_SPLIT16_LAUNCH(false, TC_, false, NTN_, true) else PWG_SPLIT16_LAUNCH(false, TC_, false, NTN_, false) }
   if (tap_center == 1) {
     if (half) {
-      if (first) PWG_SPLIT16_LAUNCH(false, 1, true, 1) else PWG_SPLIT16_LAUNCH(false, 1, false, 1)
+      if (first) PWG_SPLIT16_LAUNCH(false, 1, true, 1, false) else PWG_SPLIT16_MIDDLE(1, 1)
     }
-    if (first) PWG_SPLIT16_LAUNCH(false, 1, true, 2)
-    if (last) PWG_SPLIT16_LAUNCH(true, 1, false, 2) else PWG_SPLIT16_LAUNCH(false, 1, false, 2)
+    if (first) PWG_SPLIT16_LAUNCH(false, 1, true, 2, false)
+    if (last) PWG_SPLIT16_LAUNCH(true, 1, false, 2, false) else PWG_SPLIT16_MIDDLE(1, 2)
   } else if (tap_center == 2) {
     if (half) {
-      if (first) PWG_SPLIT16_LAUNCH(false, 2, true, 1) else PWG_SPLIT16_LAUNCH(false, 2, false, 1)
+      if (first) PWG_SPLIT16_LAUNCH(false, 2, true, 1, false) else PWG_SPLIT16_MIDDLE(2, 1)
     }
-    if (first) PWG_SPLIT16_LAUNCH(false, 2, true, 2)
-    if (last) PWG_SPLIT16_LAUNCH(true, 2, false, 2) else PWG_SPLIT16_LAUNCH(false, 2, false, 2)
+    if (first) PWG_SPLIT16_LAUNCH(false, 2, true, 2, false)
+    if (last) PWG_SPLIT16_LAUNCH(true, 2, false, 2, false) else PWG_SPLIT16_MIDDLE(2, 2)
   }
+#undef PWG_SPLIT16_MIDDLE
 #undef PWG_SPLIT16_LAUNCH
   return hipErrorInvalidValue;
 }
