@@ -5,9 +5,11 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
   Engine                    lower-level batch engine over the C-ABI (include/pwg.h)
   GraphedRun                one plan's forward captured as a HIP graph (pwg_graph_create) for
                             repeated shapes
+  DiscreteSymbolHiFiGANGenerator  drop-in token vocoder (HIP embedding front end + HiFiGAN body)
 """
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
+from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
 from .models import ParallelWaveGANGenerator  # noqa: F401
 
 __version__ = "0.1.0"

@@ -27,10 +27,12 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_rccl.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_mstack.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_rstack.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_embed.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
     os.path.join(REPO_DIR, "include", "pwg_cnet.h"),
+    os.path.join(REPO_DIR, "include", "pwg_embed.h"),
     os.path.join(PKG_DIR, "csrc", "pwg_internal.h"),
 ]
 OFFLOAD_ARCH = "gfx950"
@@ -102,6 +104,8 @@ EXPORTED_SYMBOLS = (
     "pwg_cnet_release_stream",
     "pwg_rstack_debug_launches",
     "pwg_rstack_debug_probe",
+    # include/pwg_embed.h: token front end of the discrete-symbol vocoders
+    "pwg_embed_rows",
 )
 
 PWG_OPT_LAYER_KERNEL = 0
@@ -323,6 +327,8 @@ def load():
         lib.pwg_set_option.argtypes = [vp, ctypes.c_int, ctypes.c_longlong]
         lib.pwg_timing_collect.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ll)]
         lib.pwg_timing_span.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
+        lib.pwg_embed_rows.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, ll,
+                                       vp, vp, vp]
         if lib.pwg_abi_version() != 2:
             raise RuntimeError("libpwg_hip ABI version mismatch")
         _lib = lib

@@ -532,8 +532,13 @@ class CnetEngine:
     def infer(self, mels, mean=None, scale=None):
         """Ragged batch: list of (T'_u, in_channels) device tensors -> list of (T'_u*hop, out)."""
         frames = [int(m.shape[0]) for m in mels]
-        plan = self.plan(frames)
         mel = torch.cat([m.reshape(-1) for m in mels]) if len(mels) > 1 else mels[0].reshape(-1).contiguous()
+        return self.infer_rows(frames, mel, mean, scale)
+
+    def infer_rows(self, frames, mel, mean=None, scale=None):
+        """``infer`` for input rows that are already packed: ``mel`` holds sum(frames) x in_channels
+        floats, utterances back to back (what a front-end kernel wrote)."""
+        plan = self.plan(frames)
         O = self.out_channels
         out = torch.empty(plan.out_rows * O, dtype=torch.float32, device=self.device)
         self.run(plan, mel, out, mean, scale)

@@ -141,6 +141,32 @@ VOCODER_PQMF = {"mb_melgan_v2": dict(subbands=4), "mb_melgan_test": dict(subband
                 "mb_melgan_v2_causal": dict(subbands=4), "mb_melgan_causal_test": dict(subbands=4)}
 SAMPLING_RATE.update(melgan_v1=22050, mb_melgan_v2=22050, hifigan_v1=22050)
 
+# Discrete-symbol (token) HiFiGAN vocoders (models/hifigan.py:867-1097): ids in, HiFiGAN v1 body.
+#   dsym_hubert_v1  egs/vctk/hubert_voc1/conf/hifigan_hubert.v1.yaml:26-48 (16 kHz, hop 320)
+#   dsym_token_v1   egs/opencpop/token_voc1/conf/hifigan_token_16k_nodp.v1.yaml:28-48 (no speaker table)
+# ``*_test`` are reduced shapes: with a speaker table, without one, and fed features directly.
+_DSYM_V1 = dict(out_channels=1, channels=512, concat_spk_emb=False, kernel_size=7, upsample_scales=[10, 8, 2, 2],
+                upsample_kernel_sizes=[20, 16, 4, 4], resblock_kernel_sizes=[3, 7, 11],
+                resblock_dilations=[[1, 3, 5], [1, 3, 5], [1, 3, 5]], use_additional_convs=True, bias=True,
+                nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.1},
+                use_weight_norm=True)
+_DSYM_TEST = dict(in_channels=48, out_channels=1, channels=64, num_embs=11, num_spk_embs=5, spk_emb_dim=48,
+                  concat_spk_emb=False, kernel_size=7, upsample_scales=[4, 2], upsample_kernel_sizes=[8, 4],
+                  resblock_kernel_sizes=[3, 5], resblock_dilations=[[1, 3], [1, 2]], use_additional_convs=True,
+                  bias=True, nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.1},
+                  use_weight_norm=True)
+VOCODER_PARAMS.update({
+    "dsym_hifigan_test": ("DiscreteSymbolHiFiGANGenerator", dict(_DSYM_TEST)),
+    "dsym_hifigan_nospk_test": ("DiscreteSymbolHiFiGANGenerator", dict(_DSYM_TEST, num_spk_embs=0)),
+    "dsym_hifigan_feats_test": ("DiscreteSymbolHiFiGANGenerator",
+                                dict(_DSYM_TEST, num_spk_embs=0, use_embedding_feats=True)),
+    "dsym_hubert_v1": ("DiscreteSymbolHiFiGANGenerator",
+                       dict(_DSYM_V1, in_channels=512, num_embs=100, num_spk_embs=128, spk_emb_dim=512)),
+    "dsym_token_v1": ("DiscreteSymbolHiFiGANGenerator",
+                      dict(_DSYM_V1, in_channels=768, num_embs=1025, num_spk_embs=0)),
+})
+SAMPLING_RATE.update(dsym_hubert_v1=16000, dsym_token_v1=16000)
+
 
 def vocoder_params(name, **overrides):
     """(generator class name, deep-copied generator_params) of a MelGAN-family recipe."""

@@ -69,6 +69,72 @@ def _conv_bias(seq, key):
     return key + ".1.bias" if conv.bias is not None else None
 
 
+def lower_hifigan(m):
+    """The conv-network program of a HiFiGAN body (models/hifigan.py:173-192): ``m`` holds
+    input_conv, upsamples, blocks and output_conv with the layout of HiFiGANGenerator. Buffer 0 is
+    the (m.in_channels wide) feature input. Shared by HiFiGANGenerator and the discrete-symbol
+    generator (dsym.py), whose token front end writes buffer 0."""
+    P = cnet.Program(m.in_channels)
+    ic = m.input_conv
+    if isinstance(ic, causal.CausalConv1d):
+        ch = ic.conv.out_channels
+        cur = P.buffer(ch, 1)
+        P.conv("input_conv", cur, ch, [causal.conv_src(P, 0, m.in_channels, ic, "input_conv", normalize=True)],
+               bias="input_conv.conv.bias" if ic.conv.bias is not None else None)
+    else:
+        ch = ic.out_channels
+        cur = P.buffer(ch, 1)
+        P.conv("input_conv", cur, ch,
+               [P.src(0, m.in_channels, ic.kernel_size[0], 1, ic.padding[0], cnet.PAD_ZERO, 1.0,
+                      "input_conv.weight", normalize=True)],
+               bias="input_conv.bias" if ic.bias is not None else None)
+    rate = 1
+    for i in range(m.num_upsamples):
+        act, ct = m.upsamples[i][0], m.upsamples[i][1]
+        key = f"upsamples.{i}.1"
+        if isinstance(ct, causal.CausalConvTranspose1d):
+            src, s = causal.convt_src(P, cur, ch, ct, key, _slope(act))
+            ct, key, padding, output_padding = ct.deconv, key + ".deconv", 0, 0
+        else:
+            s = ct.stride[0]
+            src = P.src(cur, ch, pre_slope=_slope(act), weight=key + ".weight")
+            padding, output_padding = ct.padding[0], ct.output_padding[0]
+        rate *= s
+        up = P.buffer(ct.out_channels, rate)
+        P.convt(key, up, ct.out_channels, src, s, padding, output_padding,
+                bias=key + ".bias" if ct.bias is not None else None)
+        ch = ct.out_channels
+        acc = P.buffer(ch, rate)
+        for j in range(m.num_blocks):
+            blk = m.blocks[i * m.num_blocks + j]
+            bkey = f"blocks.{i * m.num_blocks + j}"
+            x = up
+            nd = len(blk.convs1)
+            for d in range(nd):
+                last = d == nd - 1
+                c1 = blk.convs1[d]
+                k1 = f"{bkey}.convs1.{d}"
+                fin = dict(accumulate=j > 0, out_div=float(m.num_blocks) if j == m.num_blocks - 1 else 1.0)
+                if blk.use_additional_convs:
+                    t = P.buffer(ch, rate)
+                    P.conv(k1, t, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1))
+                    c2 = blk.convs2[d]
+                    k2 = f"{bkey}.convs2.{d}"
+                    dst = acc if last else P.buffer(ch, rate)
+                    P.conv(k2, dst, ch, [_conv_src(P, t, ch, c2, k2)], bias=_conv_bias(c2, k2), res=x,
+                           **(fin if last else {}))
+                else:
+                    dst = acc if last else P.buffer(ch, rate)
+                    P.conv(k1, dst, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1), res=x,
+                           **(fin if last else {}))
+                x = dst
+        cur = acc
+    out = P.buffer(m.out_channels, rate)
+    P.conv("output_conv.1", out, m.out_channels, [_conv_src(P, cur, ch, m.output_conv, "output_conv")],
+           bias=_conv_bias(m.output_conv, "output_conv"), post_act=cnet.ACT_TANH)
+    return P
+
+
 class HiFiGANGenerator(torch.nn.Module):
     """models/hifigan.py:23-265, executed on the MI355X conv-network engine."""
 
@@ -164,65 +230,7 @@ class HiFiGANGenerator(torch.nn.Module):
 
     # ------------------------------------------------------------------ lowering
     def program(self):
-        P = cnet.Program(self.in_channels)
-        ic = self.input_conv
-        if isinstance(ic, causal.CausalConv1d):
-            ch = ic.conv.out_channels
-            cur = P.buffer(ch, 1)
-            P.conv("input_conv", cur, ch, [causal.conv_src(P, 0, self.in_channels, ic, "input_conv", normalize=True)],
-                   bias="input_conv.conv.bias" if ic.conv.bias is not None else None)
-        else:
-            ch = ic.out_channels
-            cur = P.buffer(ch, 1)
-            P.conv("input_conv", cur, ch,
-                   [P.src(0, self.in_channels, ic.kernel_size[0], 1, ic.padding[0], cnet.PAD_ZERO, 1.0,
-                          "input_conv.weight", normalize=True)],
-                   bias="input_conv.bias" if ic.bias is not None else None)
-        rate = 1
-        for i in range(self.num_upsamples):
-            act, ct = self.upsamples[i][0], self.upsamples[i][1]
-            key = f"upsamples.{i}.1"
-            if isinstance(ct, causal.CausalConvTranspose1d):
-                src, s = causal.convt_src(P, cur, ch, ct, key, _slope(act))
-                ct, key, padding, output_padding = ct.deconv, key + ".deconv", 0, 0
-            else:
-                s = ct.stride[0]
-                src = P.src(cur, ch, pre_slope=_slope(act), weight=key + ".weight")
-                padding, output_padding = ct.padding[0], ct.output_padding[0]
-            rate *= s
-            up = P.buffer(ct.out_channels, rate)
-            P.convt(key, up, ct.out_channels, src, s, padding, output_padding,
-                    bias=key + ".bias" if ct.bias is not None else None)
-            ch = ct.out_channels
-            acc = P.buffer(ch, rate)
-            for j in range(self.num_blocks):
-                blk = self.blocks[i * self.num_blocks + j]
-                bkey = f"blocks.{i * self.num_blocks + j}"
-                x = up
-                nd = len(blk.convs1)
-                for d in range(nd):
-                    last = d == nd - 1
-                    c1 = blk.convs1[d]
-                    k1 = f"{bkey}.convs1.{d}"
-                    fin = dict(accumulate=j > 0, out_div=float(self.num_blocks) if j == self.num_blocks - 1 else 1.0)
-                    if blk.use_additional_convs:
-                        t = P.buffer(ch, rate)
-                        P.conv(k1, t, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1))
-                        c2 = blk.convs2[d]
-                        k2 = f"{bkey}.convs2.{d}"
-                        dst = acc if last else P.buffer(ch, rate)
-                        P.conv(k2, dst, ch, [_conv_src(P, t, ch, c2, k2)], bias=_conv_bias(c2, k2), res=x,
-                               **(fin if last else {}))
-                    else:
-                        dst = acc if last else P.buffer(ch, rate)
-                        P.conv(k1, dst, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1), res=x,
-                               **(fin if last else {}))
-                    x = dst
-            cur = acc
-        out = P.buffer(self.out_channels, rate)
-        P.conv("output_conv.1", out, self.out_channels, [_conv_src(P, cur, ch, self.output_conv, "output_conv")],
-               bias=_conv_bias(self.output_conv, "output_conv"), post_act=cnet.ACT_TANH)
-        return P
+        return lower_hifigan(self)
 
     # ------------------------------------------------------------------ engine plumbing
     def _device(self):

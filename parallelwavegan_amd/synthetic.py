@@ -118,7 +118,8 @@ def make_module_state_dict(module, seed=0, gain=1.0, bias_std=0.05, weight_norm=
     ~ N(0, gain^2 / fan_in) with fan_in = C_in*K (Conv1d) or C_in*2 (ConvTranspose1d, 2 taps per
     output), biases ~ N(0, bias_std^2). Keys follow the module's state dict: with weight norm
     applied, ``weight_v`` = the drawn weight and ``weight_g`` = ||v|| * U(0.5, 1.5) per output
-    slice. Buffers (PQMF filters, stats) are left out."""
+    slice. Embedding tables ~ N(0, 1) (torch.nn.Embedding's initialisation). Buffers (PQMF filters,
+    stats) are left out."""
     import torch
 
     rs = np.random.RandomState(seed)
@@ -129,14 +130,17 @@ def make_module_state_dict(module, seed=0, gain=1.0, bias_std=0.05, weight_norm=
             kinds[name] = ("convt", m.in_channels * 2)
         elif isinstance(m, torch.nn.Conv1d):
             kinds[name] = ("conv", m.in_channels * m.kernel_size[0])
+        elif isinstance(m, torch.nn.Embedding):
+            kinds[name] = ("emb", 1)
     for key, p in module.named_parameters():
         base, leaf = key.rsplit(".", 1)
         shape = tuple(p.shape)
         if leaf == "bias":
             sd[key] = (bias_std * rs.standard_normal(shape)).astype(np.float32)
         elif leaf in ("weight", "weight_v"):
-            fan = kinds[base][1]
-            w = (gain / np.sqrt(fan) * rs.standard_normal(shape)).astype(np.float32)
+            kind, fan = kinds[base]
+            std = 1.0 if kind == "emb" else gain / np.sqrt(fan)
+            w = (std * rs.standard_normal(shape)).astype(np.float32)
             sd[key] = w
             if leaf == "weight_v":
                 axes = tuple(range(1, w.ndim))

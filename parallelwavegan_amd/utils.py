@@ -18,16 +18,18 @@ import numpy as np
 import torch
 import yaml
 
-GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator")
+GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator", "DiscreteSymbolHiFiGANGenerator")
 
 
 def generator_class(name):
+    from .dsym import DiscreteSymbolHiFiGANGenerator
     from .hifigan import HiFiGANGenerator
     from .melgan import MelGANGenerator
     from .models import ParallelWaveGANGenerator
 
     table = {"ParallelWaveGANGenerator": ParallelWaveGANGenerator, "MelGANGenerator": MelGANGenerator,
-             "HiFiGANGenerator": HiFiGANGenerator}
+             "HiFiGANGenerator": HiFiGANGenerator,
+             "DiscreteSymbolHiFiGANGenerator": DiscreteSymbolHiFiGANGenerator}
     if name not in table:
         raise NotImplementedError(f"generator_type {name!r} is not accelerated (supported: {', '.join(GENERATORS)})")
     return table[name]
