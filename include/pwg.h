@@ -244,15 +244,23 @@ enum {
   PWG_OPT_SYNC_ABORT = 7,      /* test hook: 1 makes every grid-synchronised launch take its "GPU shared"
                                     exit (no output, PWG_ERR_RERUN from pwg_run_status), so the
                                     caller's rerun path can be tested; default 0 */
-  PWG_OPT_SYNC_TIMEOUT = 8     /* test hook: 1 makes every grid-barrier wait of a grid-synchronised
+  PWG_OPT_SYNC_TIMEOUT = 8,    /* test hook: 1 makes every grid-barrier wait of a grid-synchronised
                                     launch give up at once (its workgroups run ahead on partial
                                     planes, status bit 8, NaN audio, PWG_ERR_RERUN from
                                     pwg_run_status); default 0 */
+  PWG_OPT_FRAGMENT_AHEAD = 9   /* split16 per-layer launches: 1 takes the kernels that read each
+                                    MFMA step's weight fragments from LDS one step ahead, with
+                                    counted waits (default); 0 the kernels that leave the reads to the
+                                    compiler. Bit-identical. The grid-synchronised and pipelined
+                                    launches have the second form only. */
 };
 #define PWG_PIPE_MAX_DEFAULT 0LL /* off: measured slower than the per-layer launches */
 PWG_API int pwg_set_option(PwgHandle* h, int option, long long value);
 /* Current value of an option (the layer kernel the handle picked for its shape, ...). */
 PWG_API int pwg_get_option(const PwgHandle* h, int option, long long* value);
+/* How many residual-layer launches of the handle's most recent pwg_run (or graph capture) took the
+ * PWG_OPT_FRAGMENT_AHEAD form. */
+PWG_API int pwg_fragment_ahead_launches(const PwgHandle* h, long long* launches);
 
 /* Per-kernel HIP-event timing of pwg_run (off by default). collect synchronises
  * on the recorded events, adds ms and launch counts per PWG_KERNEL_* bucket into

@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = (
     "pwg_graph_destroy",
     "pwg_set_option",
     "pwg_get_option",
+    "pwg_fragment_ahead_launches",
     "pwg_set_timing",
     "pwg_release_stream",
     "pwg_timing_collect",
@@ -117,6 +118,7 @@ PWG_OPT_HALF_BLOCKS = 5
 PWG_OPT_SYNC = 6
 PWG_OPT_SYNC_ABORT = 7
 PWG_OPT_SYNC_TIMEOUT = 8
+PWG_OPT_FRAGMENT_AHEAD = 9
 
 
 class PwgConfig(ctypes.Structure):
@@ -318,6 +320,7 @@ def load():
         lib.pwg_graph_destroy.argtypes = [vp]
         lib.pwg_graph_destroy.restype = None
         lib.pwg_get_option.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ll)]
+        lib.pwg_fragment_ahead_launches.argtypes = [vp, ctypes.POINTER(ll)]
         lib.pwg_rccl_unique_id.argtypes = [vp]
         lib.pwg_rccl_comm_create.argtypes = [ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
         lib.pwg_rccl_comm_destroy.argtypes = [vp]

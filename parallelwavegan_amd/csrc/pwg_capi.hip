@@ -377,6 +377,8 @@ struct PwgHandle {
   long long pipe_max = PWG_PIPE_MAX_DEFAULT;  // PWG_OPT_PIPELINE: largest padded plan on the layer pipeline
   int sync_abort = 0;       // PWG_OPT_SYNC_ABORT (test hook)
   int sync_timeout = 0;     // PWG_OPT_SYNC_TIMEOUT (test hook)
+  int frag_ahead = 1;       // PWG_OPT_FRAGMENT_AHEAD
+  long long fa_launches = 0;  // pwg_fragment_ahead_launches: launches of the last run in that form
   long long sync_max = -1;  // PWG_OPT_SYNC: most 32-sample blocks on the grid-synchronised forward (-1: 64 x n_cu)
   long long half_max = -1;  // PWG_OPT_HALF_BLOCKS: most blocks of a half-block launch (-1: 4 x n_cu)
   int n_cu = 0;
@@ -1009,6 +1011,7 @@ static int pwg_run_impl(PwgPlan* p, const float* packed, const float* mel, const
   if (mean != nullptr && p->layout != PWG_LAYOUT_INFERENCE)
     return fail(PWG_ERR_INVALID, "normalize_before is an inference() option");
   PwgHandle* h = p->h;
+  h->fa_launches = 0;
   DeviceGuard g(h->device);
   if (!g.ok) return fail(PWG_ERR_HIP, "hipSetDevice failed");
   if (h->n_cu == 0) {
@@ -1324,8 +1327,11 @@ static int pwg_run_impl(PwgPlan* p, const float* packed, const float* mel, const
         }
         sa.trace = h->d_trace + per_layer_s * (l % 64);
       }
+      const bool frag_ahead =
+          split16 && h->frag_ahead && split16_has_fragment_ahead(last, sa.noise != nullptr, half);
+      if (frag_ahead) ++h->fa_launches;
       e = timed(PWG_KERNEL_RESIDUAL_LAYER, [&] {
-        return split16 ? launch_layer_split16(sa, last, la.tap_center, launch_w, nwg, s, half)
+        return split16 ? launch_layer_split16(sa, last, la.tap_center, launch_w, nwg, s, half, frag_ahead)
                        : launch_layer_split(sa, last, la.tap_center, wpw, nwg, s);
       });
       if (e == hipSuccess && last && trace_on) {
@@ -1526,6 +1532,10 @@ int pwg_set_option(PwgHandle* h, int option, long long value) {
       if (value != 0 && value != 1) return fail(PWG_ERR_INVALID, "sync_timeout must be 0 or 1");
       h->sync_timeout = (int)value;
       return PWG_OK;
+    case PWG_OPT_FRAGMENT_AHEAD:
+      if (value != 0 && value != 1) return fail(PWG_ERR_INVALID, "fragment_ahead must be 0 or 1");
+      h->frag_ahead = (int)value;
+      return PWG_OK;
 
     default:
       return fail(PWG_ERR_INVALID, "unknown option");
@@ -1544,9 +1554,16 @@ int pwg_get_option(const PwgHandle* h, int option, long long* value) {
     case PWG_OPT_SYNC: *value = h->sync_max >= 0 ? h->sync_max : 64LL * h->n_cu; return PWG_OK;
     case PWG_OPT_SYNC_ABORT: *value = h->sync_abort; return PWG_OK;
     case PWG_OPT_SYNC_TIMEOUT: *value = h->sync_timeout; return PWG_OK;
+    case PWG_OPT_FRAGMENT_AHEAD: *value = h->frag_ahead; return PWG_OK;
 
     default: return fail(PWG_ERR_INVALID, "unknown option");
   }
+}
+
+int pwg_fragment_ahead_launches(const PwgHandle* h, long long* launches) {
+  if (!h || !launches) return fail(PWG_ERR_INVALID, "null argument");
+  *launches = h->fa_launches;
+  return PWG_OK;
 }
 
 int pwg_release_stream(PwgHandle* h, void* stream) {

@@ -96,6 +96,57 @@ __device__ __forceinline__ void seed8x(const u32x4 h, const u32x4 l, const f32x4
         "v"(b1[0]), "v"(b1[1]), "v"(b1[2]), "v"(b1[3]), "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));
 }
 
+// ---- A fragments read one step ahead of their MFMAs (s16_block with FA) ----------------------
+// The compiler sinks a plain LDS read next to its first use however the source orders it, so each
+// (ks, m) step of a GEMM exposed a full LDS latency in front of its six MFMAs. Here the reads and
+// their waits are explicit. fa_read issues the hi and lo fragment of one step (2 ds_read_b128,
+// 1 KB apart) into a slot; fa_wait<N> waits until at most N LGKM operations are outstanding and
+// passes the slot through as "+v", so no MFMA that uses the slot can be placed above the wait and
+// nothing touches the registers between the read and the wait (both are volatile and stay in
+// program order).
+// Why a counted wait is enough although the compiler knows nothing of these reads: LDS reads
+// return in issue order, and N is never more than the number of OUR reads issued after the slot's
+// pair. If one read of the pair were still outstanding, so would be those N younger reads, N + 1
+// in all, whatever else (the compiler's own LDS reads, scalar loads, which may return out of
+// order) is in flight: more than the wait lets through. Other operations in flight only make the
+// wait stricter. The other way round, the compiler's own counted waits see a counter that our
+// reads can only raise, so they wait for no less than they did.
+// The leading s_nop 6: the register allocator may hand fa_read a register that an MFMA just wrote
+// or read as its accumulator input (the temporaries of the zero-initialised first k-step), and
+// the compiler, which does not look inside the asm, adds none of the wait states it puts between
+// such an MFMA and an LDS load of its own (7 after a 4-pass MFMA's write, 3 after its SrcC read).
+// The 7 idle cycles fall into the 16 cycles of the step's last MFMA.
+template <int OFF>
+__device__ __forceinline__ void fa_read(u32x4& h, u32x4& l, unsigned addr) {
+  static_assert(OFF >= 0 && OFF + 1024 < 65536, "ds_read offset field");
+  asm volatile(
+      "s_nop 6\n\t"
+      "ds_read_b128 %0, %2 offset:%3\n\t"
+      "ds_read_b128 %1, %2 offset:%4"
+      : "=&v"(h), "=&v"(l)
+      : "v"(addr), "i"(OFF), "i"(OFF + 1024));
+}
+template <int N>
+__device__ __forceinline__ void fa_wait(u32x4& h, u32x4& l) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(h), "+v"(l) : "i"(N));
+}
+// byte address of an LDS location as ds_read takes it
+__device__ __forceinline__ unsigned lds_addr(const void* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const void*)p;
+}
+// f(IC<0>) ... f(IC<N - 1>): a loop whose index is a constant expression inside the body
+template <int I>
+struct IC {
+  static constexpr int value = I;
+};
+template <int I, int N, typename F>
+__device__ __forceinline__ void fa_for(F&& f) {
+  if constexpr (I < N) {
+    f(IC<I>{});
+    fa_for<I + 1, N>(f);
+  }
+}
+
 struct Pair16 {
   unsigned hi, lo;
 };
@@ -318,7 +369,10 @@ __device__ __forceinline__ void s16_load_skip(const SplitArgs& a, const BlockDes
 // bd_v, bdn_v, h16_v, h16n_v: as loaded (per-lane registers holding wave-uniform values); the body
 // works on their scalar copies, so its index math is SALU and its addresses are a uniform base
 // plus a 32-bit lane offset. AL: as s16_bload.
-template <bool LAST, int TC, bool FIRST, bool PIPE, int NTN = 2, bool AL = false, typename Mid>
+// FA: the A fragments of GEMM 1 and GEMM 2 are read one (ks, m) step ahead of their MFMAs into
+// two rotating slots (fa_read / fa_wait above), across tap boundaries and from the end of GEMM 1
+// into GEMM 2. Same MFMAs in the same order per accumulator: bit-identical to !FA.
+template <bool LAST, int TC, bool FIRST, bool PIPE, int NTN = 2, bool AL = false, bool FA = false, typename Mid>
 __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* smem16, const BlockDesc& bd_v,
                                           const BlockDesc& bdn_v, bool has_next, u32x4 (&b0)[8], u32x4 (&b1)[8],
                                           bool& nonfinite, Mid&& mid, int h16_v = 0, int h16n_v = 0,
@@ -404,6 +458,35 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
       }
     }
   };
+  // FA: fragment (ks, m, hi/lo) of image `img` (taps 0..2 of GEMM 1, 3 = GEMM 2) lies at
+  // fa_base + img * 32 KB + ((ks * 8 + m) * 2 + hl) * 1 KB: one address per image, the rest in the
+  // 16-bit offset field. A step's pair sits in slot (step & 1); every image has an even step
+  // count, so the slots keep alternating across images.
+  constexpr int FA_IMG = 2 * 8 * 2 * 64 * 16;
+  const unsigned fa_base = FA ? lds_addr(smem16) + 16u * (unsigned)lane : 0u;
+  u32x4 fh[2], fl[2];
+  // One tap of GEMM 1 with its step-0 pair already in flight in slot 0. Each step issues the
+  // next step's pair (the last one: step 0 of image `nxt`) before its own wait, so the wait lets
+  // exactly that pair stay outstanding. The sched_barrier closing a step keeps its six MFMAs in
+  // it: left free, the scheduler collects the lo-fragment MFMAs of a k-step at its end and holds
+  // all eight lo fragments live (246 VGPRs instead of 222, and the reads no longer a step apart).
+  auto mma_tap_fa = [&](f32x4 (&acc)[8][2], const u32x4 (&b)[8], int tap, int nxt) {
+    const unsigned here = fa_base + (unsigned)(tap * FA_IMG), there = fa_base + (unsigned)(nxt * FA_IMG);
+    fa_for<0, 16>([&](auto sc) {
+      constexpr int s = decltype(sc)::value, ks = s >> 3, m = s & 7, cur = s & 1;
+      if constexpr (s < 15) fa_read<(s + 1) * 2048>(fh[cur ^ 1], fl[cur ^ 1], here);
+      else fa_read<0>(fh[cur ^ 1], fl[cur ^ 1], there);
+      fa_wait<2>(fh[cur], fl[cur]);
+#pragma unroll
+      for (int nt = 0; nt < NTN; ++nt) {
+        f32x4& ac = acc[m][nt];
+        ac = mma16(fh[cur], b[nt * 4 + ks * 2], ac);
+        ac = mma16(fh[cur], b[nt * 4 + ks * 2 + 1], ac);
+        ac = mma16(fl[cur], b[nt * 4 + ks * 2], ac);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
 
   // ---- GEMM 1: taps 0, other, center (the center row becomes the GEMM-2 seeds at the end)
   f32x4 acc[8][2];
@@ -412,12 +495,19 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt) acc[m][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 acc2[8][2];
+  if constexpr (FA) fa_read<0>(fh[0], fl[0], fa_base);
   s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bd, T1, b1, g, c, h16);
-  mma_tap(acc, b0, 0);
+  if constexpr (FA) mma_tap_fa(acc, b0, 0, T1);
+  else mma_tap(acc, b0, 0);
   s16_load_dv(a, bd, dv, g, c);
   s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bd, TC, b0, g, c, h16);
-  mma_tap(acc, b1, T1);
-  mma_tap(acc, b0, TC);
+  if constexpr (FA) {
+    mma_tap_fa(acc, b1, T1, TC);
+    mma_tap_fa(acc, b0, TC, 3);  // its last step issues GEMM 2's first pair, in flight through the gate
+  } else {
+    mma_tap(acc, b1, T1);
+    mma_tap(acc, b0, TC);
+  }
   if (!LAST) {
     // GEMM-2 out-row seeds sqrt(.5)(x + b_out) from the center tap: acc2[4 + 2ks + (j>>2)][nt][j&3]
     const f32x4* bo_l = reinterpret_cast<const f32x4*>(s_bo + 16 * g);
@@ -491,6 +581,28 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
   // ---- GEMM 2: [skip; out] rows, 8 m-tiles (last layer: the 4 skip tiles)
   constexpr int M2 = LAST ? 4 : 8;
   const u32x4* w2l = reinterpret_cast<const u32x4*>(s_w2) + lane;
+  if constexpr (FA) {
+    // steps (ks, m < M2); step 0's pair was issued by GEMM 1's last step
+    const unsigned here = fa_base + 3u * FA_IMG;
+    fa_for<0, 2 * M2>([&](auto sc) {
+      constexpr int s = decltype(sc)::value, ks = s / M2, m = s % M2, cur = s & 1;
+      constexpr int sn = s + 1, fn = (sn / M2) * 8 + sn % M2;  // the next step's fragment index
+      if constexpr (sn < 2 * M2) {
+        fa_read<fn * 2048>(fh[cur ^ 1], fl[cur ^ 1], here);
+        fa_wait<2>(fh[cur], fl[cur]);
+      } else {
+        fa_wait<0>(fh[cur], fl[cur]);
+      }
+#pragma unroll
+      for (int nt = 0; nt < NTN; ++nt) {
+        f32x4& ac = acc2[m][nt];
+        ac = mma16(fh[cur], gh[nt][ks], ac);
+        ac = mma16(fh[cur], gl[nt][ks], ac);
+        ac = mma16(fl[cur], gh[nt][ks], ac);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  } else {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -512,6 +624,7 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
         }
       __builtin_amdgcn_sched_barrier(0);
     }
+  }
 
   if (!LAST) {
     const Plane16<PIPE> skip(a.skip), xo(a.x_out);
@@ -629,10 +742,11 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
 // NTN = 1 (small plans, the B = 1 latency path): the work unit is half a block (one 16-column
 // n-tile; unit u = block u / 2, columns 16 (u % 2) + [0, 16)), so twice the waves share a layer and
 // each wave's dependent chain runs half the MFMAs; bit-identical to whole blocks.
-// AL: the layer's dilation is a multiple of 16 (s16_bload; the host knows it). NTN stays the last
+// AL: the layer's dilation is a multiple of 16 (s16_bload; the host knows it). FA: the block body
+// reads its A fragments a step ahead (s16_block; PWG_OPT_FRAGMENT_AHEAD). NTN stays the last
 // template argument: bench.py tells the kernels apart by their names, where a name ending in
 // ", true>" does not count as a middle layer.
-template <bool LAST, int TC, bool FIRST, bool AL, int NTN>
+template <bool LAST, int TC, bool FIRST, bool AL, bool FA, int NTN>
 __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitArgs a) {
   constexpr int UB = NTN == 1 ? 1 : 0;  // log2(units per block)
   const int n_units = a.n_blocks << UB;
@@ -731,7 +845,7 @@ __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitAr
     bdn = a.blocks[pf >> UB];
     h16n = NTN == 1 ? 16 * (pf & 1) : 0;
     int ticket = 0;
-    s16_block<LAST, TC, FIRST, false, NTN, AL>(a, smem16, bd, bdn, true, b0, b1, nonfinite, [&]() {
+    s16_block<LAST, TC, FIRST, false, NTN, AL, FA>(a, smem16, bd, bdn, true, b0, b1, nonfinite, [&]() {
       if (nblk >= 0) ticket = ticket_issue();
     }, h16, h16n, poison);
     if (tr && n_done++ == 0) t_first = __builtin_amdgcn_s_memrealtime();
@@ -1028,23 +1142,40 @@ hipError_t launch_first_conv_split16(const FirstConvArgs& a, long long n_tiles, 
   return hipGetLastError();
 }
 
+// Which per-layer kernels exist in the read-ahead form (FA): those that take it without a VGPR
+// spill or scratch. All do (register table: with each step's MFMAs pinned the body
+// needs fewer registers than before, the whole-block fused first_conv kernel 226-228 instead of
+// 256); a role that ever stops fitting is switched off here and keeps the other form.
+constexpr bool FA_MIDDLE = true, FA_LAST = true, FA_FIRST_HALF = true, FA_FIRST_WHOLE = true;
+
+bool split16_has_fragment_ahead(bool last, bool first, bool half) {
+  return last ? FA_LAST : first ? (half ? FA_FIRST_HALF : FA_FIRST_WHOLE) : FA_MIDDLE;
+}
+
 hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, int waves_per_wg, int n_wg,
-                                hipStream_t s, bool half) {
+                                hipStream_t s, bool half, bool frag_ahead) {
   if (waves_per_wg > 8) waves_per_wg = 8;
   if (a.compute_waves < 1 || a.compute_waves > waves_per_wg) return hipErrorInvalidValue;
   if (half && last) return hipErrorInvalidValue;  // the head needs both n-tiles of a block
   const dim3 grid((unsigned)n_wg), block((unsigned)(64 * waves_per_wg));
-#define PWG_SPLIT16_LAUNCH(LAST_, TC_, FIRST_, NTN_, AL_)                                               \
+#define PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, FA_)                                       \
   {                                                                                                     \
     const size_t lds = sizeof(unsigned) * (Split16Smem::dwords(LAST_) + (FIRST_ ? 128 : 0));            \
-    auto kfn = &pwg_layer_split16_kernel<LAST_, TC_, FIRST_, AL_, NTN_>;                                \
+    auto kfn = &pwg_layer_split16_kernel<LAST_, TC_, FIRST_, AL_, FA_, NTN_>;                           \
     hipError_t e_ = allow_lds(reinterpret_cast<const void*>(kfn), (int)lds);                           \
     if (e_ != hipSuccess) return e_;                                                                    \
     hipLaunchKernelGGL(kfn, grid, block, lds, s, a);                                                    \
     return hipGetLastError();                                                                           \
   }
+#define PWG_SPLIT16_LAUNCH(LAST_, TC_, FIRST_, NTN_, AL_)                                               \
+  {                                                                                                     \
+    if constexpr (LAST_ ? FA_LAST : FIRST_ ? (NTN_ == 1 ? FA_FIRST_HALF : FA_FIRST_WHOLE) : FA_MIDDLE) \
+      if (frag_ahead) PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, true)                        \
+    PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, false)                                         \
+  }
   const bool first = a.noise != nullptr;  // fused first_conv (never together with last: L > 1)
   if (first && last) return hipErrorInvalidValue;
+  if (frag_ahead && !split16_has_fragment_ahead(last, first, half)) return hipErrorInvalidValue;
   // middle layers: taps shifted by a multiple of 16 columns keep the constant lane offset
   const bool al = a.dil % 16 == 0;
 #define PWG_SPLIT16_MIDDLE(TC_, NTN_) \
@@ -1064,6 +1195,7 @@ hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, i
   }
 #undef PWG_SPLIT16_MIDDLE
 #undef PWG_SPLIT16_LAUNCH
+#undef PWG_SPLIT16_LAUNCH_FA
   return hipErrorInvalidValue;
 }
 

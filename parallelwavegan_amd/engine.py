@@ -418,7 +418,7 @@ class Engine:
 
     def set_option(self, option, value):
         """pwg_set_option: option in {"layer_kernel", "waves_per_wg", "wg_per_cu", "fuse_first_conv",
-        "pipeline", "half_blocks", "sync"}. "pipeline" (largest padded plan on the layer-pipelined launch, 0 = never)
+        "pipeline", "half_blocks", "sync", "fragment_ahead"}. "pipeline" (largest padded plan on the layer-pipelined launch, 0 = never)
         applies to plans created afterwards: the cached plans are dropped."""
         opts = self._OPTS
         if option == "layer_kernel" and isinstance(value, str):
@@ -435,13 +435,20 @@ class Engine:
              "wg_per_cu": _lib.PWG_OPT_WG_PER_CU, "fuse_first_conv": _lib.PWG_OPT_FUSE_FIRST_CONV,
              "pipeline": _lib.PWG_OPT_PIPELINE, "half_blocks": _lib.PWG_OPT_HALF_BLOCKS,
              "sync": _lib.PWG_OPT_SYNC, "sync_abort": _lib.PWG_OPT_SYNC_ABORT,
-             "sync_timeout": _lib.PWG_OPT_SYNC_TIMEOUT}
+             "sync_timeout": _lib.PWG_OPT_SYNC_TIMEOUT, "fragment_ahead": _lib.PWG_OPT_FRAGMENT_AHEAD}
     SYNC_FAIL_STREAK = 3
     SYNC_RETRY_RUNS = 256
 
     def get_option(self, option):
         v = ctypes.c_longlong()
         _lib.check(self._lib.pwg_get_option(self._h, self._OPTS[option], ctypes.byref(v)))
+        return int(v.value)
+
+    def fragment_ahead_launches(self):
+        """pwg_fragment_ahead_launches: residual-layer launches of the most recent forward that took
+        the "fragment_ahead" kernels."""
+        v = ctypes.c_longlong()
+        _lib.check(self._lib.pwg_fragment_ahead_launches(self._h, ctypes.byref(v)))
         return int(v.value)
 
     # ---------------------------------------------------------------- timing
