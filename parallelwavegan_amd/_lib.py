@@ -28,11 +28,13 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_mstack.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_rstack.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_embed.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_smg.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
     os.path.join(REPO_DIR, "include", "pwg_cnet.h"),
     os.path.join(REPO_DIR, "include", "pwg_embed.h"),
+    os.path.join(REPO_DIR, "include", "pwg_smg.h"),
     os.path.join(PKG_DIR, "csrc", "pwg_internal.h"),
 ]
 OFFLOAD_ARCH = "gfx950"
@@ -107,6 +109,22 @@ EXPORTED_SYMBOLS = (
     "pwg_rstack_debug_probe",
     # include/pwg_embed.h: token front end of the discrete-symbol vocoders
     "pwg_embed_rows",
+    # include/pwg_smg.h: StyleMelGAN generator path
+    "pwg_smg_create",
+    "pwg_smg_destroy",
+    "pwg_smg_ref_weight_count",
+    "pwg_smg_packed_weight_count",
+    "pwg_smg_pack_weights",
+    "pwg_smg_plan_create",
+    "pwg_smg_plan_destroy",
+    "pwg_smg_plan_workspace_bytes",
+    "pwg_smg_plan_out_rows",
+    "pwg_smg_run",
+    "pwg_smg_run_status",
+    "pwg_smg_plan_tensor",
+    "pwg_smg_debug_stats",
+    "pwg_smg_set_timing",
+    "pwg_smg_timing_collect",
 )
 
 PWG_OPT_LAYER_KERNEL = 0
@@ -119,6 +137,31 @@ PWG_OPT_SYNC = 6
 PWG_OPT_SYNC_ABORT = 7
 PWG_OPT_SYNC_TIMEOUT = 8
 PWG_OPT_FRAGMENT_AHEAD = 9
+
+
+PWG_SMG_MAX_SCALES = 16
+PWG_SMG_STATS_TILE = 128
+PWG_SMG_GATES = {"softmax": 0, "sigmoid": 1}
+PWG_SMG_X_IN, PWG_SMG_X_OUT, PWG_SMG_STATS_IN, PWG_SMG_STATS_MID = range(4)
+PWG_SMG_KINDS = ("noise", "stats", "aux_conv", "modulate_conv", "gate_conv", "finalise", "output")
+
+
+class PwgSmgConfig(ctypes.Structure):
+    _fields_ = [
+        ("in_channels", ctypes.c_int),
+        ("aux_channels", ctypes.c_int),
+        ("channels", ctypes.c_int),
+        ("out_channels", ctypes.c_int),
+        ("kernel_size", ctypes.c_int),
+        ("dilation", ctypes.c_int),
+        ("bias", ctypes.c_int),
+        ("gate", ctypes.c_int),
+        ("noise_slope", ctypes.c_float),
+        ("num_noise_scales", ctypes.c_int),
+        ("noise_scales", ctypes.c_int * PWG_SMG_MAX_SCALES),
+        ("num_scales", ctypes.c_int),
+        ("upsample_scales", ctypes.c_int * PWG_SMG_MAX_SCALES),
+    ]
 
 
 class PwgConfig(ctypes.Structure):
@@ -332,6 +375,24 @@ def load():
         lib.pwg_timing_span.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         lib.pwg_embed_rows.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, ll,
                                        vp, vp, vp]
+        lib.pwg_smg_create.argtypes = [ctypes.POINTER(PwgSmgConfig), ctypes.c_int, ctypes.POINTER(vp)]
+        lib.pwg_smg_destroy.argtypes = [vp]
+        lib.pwg_smg_destroy.restype = None
+        lib.pwg_smg_plan_destroy.argtypes = [vp]
+        lib.pwg_smg_plan_destroy.restype = None
+        for name in ("pwg_smg_ref_weight_count", "pwg_smg_packed_weight_count", "pwg_smg_plan_workspace_bytes",
+                     "pwg_smg_plan_out_rows"):
+            getattr(lib, name).argtypes = [vp]
+            getattr(lib, name).restype = ll
+        lib.pwg_smg_pack_weights.argtypes = [vp, vp, vp]
+        lib.pwg_smg_plan_create.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(vp)]
+        lib.pwg_smg_run.argtypes = [vp] * 9
+        lib.pwg_smg_run_status.argtypes = [vp, vp, vp]
+        lib.pwg_smg_plan_tensor.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ll), ctypes.POINTER(ll),
+                                            ctypes.POINTER(ctypes.c_int)]
+        lib.pwg_smg_debug_stats.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ll), ctypes.c_int, vp, vp, vp, vp]
+        lib.pwg_smg_set_timing.argtypes = [vp, ctypes.c_int]
+        lib.pwg_smg_timing_collect.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         if lib.pwg_abi_version() != 2:
             raise RuntimeError("libpwg_hip ABI version mismatch")
         _lib = lib

@@ -174,3 +174,36 @@ def vocoder_params(name, **overrides):
     p = copy.deepcopy(p)
     p.update(copy.deepcopy(overrides))
     return cls, p
+
+
+# StyleMelGAN generators (models/style_melgan.py:18-240), a table of their own: they run on the
+# TADE kernels (include/pwg_smg.h), not on the conv-network executor.
+#   style_melgan_v1  egs/{ljspeech,libritts,vctk,jsut,csmsc,yesno}/voc1/conf/style_melgan.v1*.yaml
+# ``*_test`` are reduced shapes: the softmax gate with even scales, and a sigmoid gate with odd
+# noise and upsample scales, with and without biases.
+STYLE_MELGAN_PARAMS = {
+    "style_melgan_v1": dict(in_channels=128, aux_channels=80, channels=64, out_channels=1, kernel_size=9, dilation=2,
+                            bias=True, noise_upsample_scales=[11, 2, 2, 2], noise_upsample_activation="LeakyReLU",
+                            noise_upsample_activation_params={"negative_slope": 0.2},
+                            upsample_scales=[2, 2, 2, 2, 2, 2, 2, 2, 1], upsample_mode="nearest",
+                            gated_function="softmax", use_weight_norm=True),
+    "style_melgan_test": dict(in_channels=32, aux_channels=80, channels=64, out_channels=1, kernel_size=9, dilation=2,
+                              bias=True, noise_upsample_scales=[4, 2], noise_upsample_activation="LeakyReLU",
+                              noise_upsample_activation_params={"negative_slope": 0.2},
+                              upsample_scales=[2, 2, 2, 1], upsample_mode="nearest", gated_function="softmax",
+                              use_weight_norm=True),
+    "style_melgan_odd_test": dict(in_channels=32, aux_channels=16, channels=32, out_channels=1, kernel_size=5,
+                                  dilation=2, bias=True, noise_upsample_scales=[3, 2],
+                                  noise_upsample_activation="LeakyReLU",
+                                  noise_upsample_activation_params={"negative_slope": 0.2},
+                                  upsample_scales=[3, 1, 2], upsample_mode="nearest", gated_function="sigmoid",
+                                  use_weight_norm=True),
+}
+STYLE_MELGAN_PARAMS["style_melgan_odd_nobias_test"] = dict(STYLE_MELGAN_PARAMS["style_melgan_odd_test"], bias=False)
+
+
+def style_melgan_params(name, **overrides):
+    """Deep-copied StyleMelGANGenerator constructor arguments of a recipe."""
+    p = copy.deepcopy(STYLE_MELGAN_PARAMS[name])
+    p.update(copy.deepcopy(overrides))
+    return p
