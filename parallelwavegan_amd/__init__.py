@@ -6,11 +6,15 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
   GraphedRun                one plan's forward captured as a HIP graph (pwg_graph_create) for
                             repeated shapes
   DiscreteSymbolHiFiGANGenerator  drop-in token vocoder (HIP embedding front end + HiFiGAN body)
+  DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator
+                            its duration- and f0-conditioned siblings (HIP duration predictor, length
+                            regulator and f0 / weighted-sum front ends)
   StyleMelGANGenerator      drop-in StyleMelGAN generator on the TADE kernels (include/pwg_smg.h)
 """
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
 from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
+from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator  # noqa: F401
 from .models import ParallelWaveGANGenerator  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401
 

@@ -28,6 +28,7 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_mstack.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_rstack.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_embed.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_embed_ext.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_smg.hip"),
 ]
 HEADERS = [
@@ -109,6 +110,11 @@ EXPORTED_SYMBOLS = (
     "pwg_rstack_debug_probe",
     # include/pwg_embed.h: token front end of the discrete-symbol vocoders
     "pwg_embed_rows",
+    # ... and of the duration- and f0-conditioned ones (csrc/pwg_embed_ext.hip)
+    "pwg_durpred_layer",
+    "pwg_regulate_scan",
+    "pwg_regulate_rows",
+    "pwg_embed_rows_f0",
     # include/pwg_smg.h: StyleMelGAN generator path
     "pwg_smg_create",
     "pwg_smg_destroy",
@@ -375,6 +381,12 @@ def load():
         lib.pwg_timing_span.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         lib.pwg_embed_rows.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, ll,
                                        vp, vp, vp]
+        ci = ctypes.c_int
+        lib.pwg_durpred_layer.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, ci, ll,
+                                          vp, vp, vp, vp, vp]
+        lib.pwg_regulate_scan.argtypes = [vp, vp, ci, ll, vp, vp, vp, vp]
+        lib.pwg_regulate_rows.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, ll, ll, vp, vp, vp]
+        lib.pwg_embed_rows_f0.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ll, vp, vp, vp]
         lib.pwg_smg_create.argtypes = [ctypes.POINTER(PwgSmgConfig), ctypes.c_int, ctypes.POINTER(vp)]
         lib.pwg_smg_destroy.argtypes = [vp]
         lib.pwg_smg_destroy.restype = None

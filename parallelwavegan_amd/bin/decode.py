@@ -11,7 +11,13 @@ Same arguments for the mel-to-wave case (--dumpdir with ``*-feats.npy`` files, -
   * features are read lazily: lengths from the .npy headers, data per batch of the rank's shard;
   * under ``torch.distributed.run`` every rank decodes its LPT share of the utterances on its own
     GPU (sharding.decode_sharded) and writes its own wavs;
-  * --scp (kaldiio), hdf5 dumps and --use-f0 are not available in this image: they raise.
+  * --scp (kaldiio) and hdf5 dumps are not available in this image: they raise;
+  * --use-f0 (DiscreteSymbolF0Generator only; any other generator raises) reads ``*-f0.npy`` beside
+    each ``*-feats.npy``, as the reference's npy branch does (bin/decode.py:185-252);
+  * DiscreteSymbolDurationGenerator decodes in three steps: the durations of a batch of token
+    sequences are predicted (predict_durations), the engine passes are then sized by the regulated
+    frame counts instead of the token counts, and the tokens are decoded with ``ds=`` (host-resident
+    durations: no further device-to-host traffic).
 """
 
 import argparse
@@ -78,8 +84,6 @@ def main(argv=None):
 
     if args.scp is not None or args.segments is not None:
         raise NotImplementedError("--scp/--segments need kaldiio, which is not available; use --dumpdir")
-    if args.use_f0:
-        raise NotImplementedError("--use-f0 generators are not accelerated")
     if args.dumpdir is None:
         raise ValueError("Please specify either --dumpdir or --feats-scp.")
     os.makedirs(args.outdir, exist_ok=True)
@@ -106,6 +110,14 @@ def main(argv=None):
     if args.normalize_before:
         assert hasattr(model, "mean"), "Feature stats are not registered."
         assert hasattr(model, "scale"), "Feature stats are not registered."
+    from parallelwavegan_amd.dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator
+
+    if args.use_f0 and not (isinstance(model, DiscreteSymbolF0Generator) and model.use_f0):
+        raise NotImplementedError(f"--use-f0 needs a DiscreteSymbolF0Generator with use_f0 (got "
+                                  f"{type(model).__name__}); other f0 generators are not accelerated")
+    if isinstance(model, DiscreteSymbolF0Generator) and model.use_f0 and not args.use_f0:
+        raise ValueError("this generator was trained with use_f0: pass --use-f0 (and dump *-f0.npy files)")
+    with_durations = isinstance(model, DiscreteSymbolDurationGenerator)
     model.remove_weight_norm()
     model = model.eval().to(device)
 
@@ -127,36 +139,59 @@ def main(argv=None):
         def fits(nfr, nutt):
             return nfr <= args.batch_frames
 
+    def load_feats(i):
+        return torch.from_numpy(np.ascontiguousarray(np.load(files[i], allow_pickle=False), np.float32))
+
+    def batches(idx, size):
+        """``idx`` cut into consecutive runs that fit one engine pass; size[i]: frames of file i."""
+        batch, nfr = [], 0
+        for slot, i in enumerate(idx):
+            if batch and not fits(nfr + size[i], len(batch) + 1):
+                yield batch
+                batch, nfr = [], 0
+            batch.append((slot, i))
+            nfr += size[i]
+        if batch:
+            yield batch
+
     def decode(idx):
         outs = [None] * len(idx)
-        batch, nfr = [], 0
         total_rtf, n = 0.0, 0
+        size, durations, predict_time = lengths, {}, {}
+        if with_durations:
+            # step 1: predicted durations per batch of token sequences; step 2 (below): the engine
+            # passes are sized by the regulated frame counts
+            size = list(lengths)
+            for batch in batches(idx, lengths):
+                start = time.time()
+                with torch.no_grad():
+                    ds = model.predict_durations([load_feats(i) for _, i in batch])
+                ds = [d.cpu().numpy() for d in ds]
+                for (_, i), d in zip(batch, ds):
+                    durations[i] = d
+                    size[i] = int(d.sum()) or len(d)  # (all-zero durations count as all ones)
+                    predict_time[i] = (time.time() - start) / len(batch)
 
-        def flush():
-            nonlocal batch, nfr, total_rtf, n
-            if not batch:
-                return
-            cs = [torch.from_numpy(np.ascontiguousarray(np.load(files[i], allow_pickle=False), np.float32))
-                  for _, i in batch]
+        for batch in batches(idx, size):
+            cs = [load_feats(i) for _, i in batch]
+            kwargs = {}
+            if args.use_f0:
+                kwargs["f0s"] = [np.ascontiguousarray(np.load(files[i].replace("-feats.npy", "-f0.npy"),
+                                                              allow_pickle=False), np.float32).reshape(-1)
+                                 for _, i in batch]
+            if with_durations:
+                kwargs["ds"] = [durations[i] for _, i in batch]
             start = time.time()
             with torch.no_grad():
-                ys = model.inference_batch(cs, normalize_before=args.normalize_before)
+                ys = model.inference_batch(cs, normalize_before=args.normalize_before, **kwargs)
                 ys = [y.view(-1).cpu().numpy() for y in ys]
-            el = time.time() - start
+            el = time.time() - start + sum(predict_time.get(i, 0.0) for _, i in batch)
             audio = sum(len(y) for y in ys) / sr
             total_rtf += el / audio * len(ys)
             n += len(ys)
             for (slot, i), y in zip(batch, ys):
                 write_pcm16_wav(os.path.join(config["outdir"], f"{utt_ids[i]}_gen.wav"), y, sr)
                 outs[slot] = len(y)
-            batch, nfr = [], 0
-
-        for slot, i in enumerate(idx):
-            if batch and not fits(nfr + lengths[i], len(batch) + 1):
-                flush()
-            batch.append((slot, i))
-            nfr += lengths[i]
-        flush()
         log_rtf(n, total_rtf)
         return outs
 

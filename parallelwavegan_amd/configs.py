@@ -167,6 +167,32 @@ VOCODER_PARAMS.update({
 })
 SAMPLING_RATE.update(dsym_hubert_v1=16000, dsym_token_v1=16000)
 
+# Duration- and f0-conditioned token vocoders (models/hifigan.py:1100-1487; dsym_variants.py).
+#   dsym_duration_v1         egs/cvss_c/hubert_voc1/conf/hifigan_hubert_duration.v1.yaml (predictor 512 -> 384)
+#   dsym_token_duration_16k  egs/opencpop/token_voc1/conf/hifigan_token_16k_duration.v1.yaml (1024 -> 384)
+#   dsym_f0_v1               egs/opencpop/token_voc1/conf/hifigan_token_16k_nodp_f0.v1.yaml (768 + 256)
+# ``*_test`` are reduced shapes on _DSYM_TEST.
+_DSYM_DUR = dict(num_spk_embs=0, duration_layers=2, duration_chans=384, duration_kernel_size=3, duration_offset=1.0,
+                 duration_dropout_rate=0.5)
+VOCODER_PARAMS.update({
+    "dsym_duration_test": ("DiscreteSymbolDurationGenerator",
+                           dict(_DSYM_TEST, num_spk_embs=0, duration_chans=32, duration_layers=2)),
+    "dsym_f0_test": ("DiscreteSymbolF0Generator", dict(_DSYM_TEST, num_spk_embs=0, linear_channel=16)),
+    "dsym_f0_spk_test": ("DiscreteSymbolF0Generator", dict(_DSYM_TEST, linear_channel=16)),
+    "dsym_f0_wsum_test": ("DiscreteSymbolF0Generator",
+                          dict(_DSYM_TEST, num_spk_embs=0, linear_channel=16, use_weight_sum=True, layer_num=3)),
+    "dsym_f0_wsum_fix_test": ("DiscreteSymbolF0Generator",
+                              dict(_DSYM_TEST, num_spk_embs=0, linear_channel=16, use_weight_sum=True, layer_num=3,
+                                   use_fix_weight=True)),
+    "dsym_duration_v1": ("DiscreteSymbolDurationGenerator",
+                         dict(_DSYM_V1, **_DSYM_DUR, in_channels=512, num_embs=500, spk_emb_dim=512)),
+    "dsym_token_duration_16k": ("DiscreteSymbolDurationGenerator",
+                                dict(_DSYM_V1, **_DSYM_DUR, in_channels=1024, num_embs=1024, spk_emb_dim=512)),
+    "dsym_f0_v1": ("DiscreteSymbolF0Generator",
+                   dict(_DSYM_V1, in_channels=768, linear_channel=256, num_embs=1025, num_spk_embs=0)),
+})
+SAMPLING_RATE.update(dsym_duration_v1=16000, dsym_token_duration_16k=16000, dsym_f0_v1=16000)
+
 
 def vocoder_params(name, **overrides):
     """(generator class name, deep-copied generator_params) of a MelGAN-family recipe."""

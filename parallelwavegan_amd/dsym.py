@@ -23,7 +23,7 @@ from . import _lib, cnet
 from .engine import WeightTracker, first_parameter
 from .hifigan import HiFiGANGenerator, HiFiGANResidualBlock
 
-BAD_TOKEN, BAD_SPEAKER = 1, 2  # include/pwg_embed.h
+BAD_TOKEN, BAD_SPEAKER, BAD_DURATION = 1, 2, 4  # include/pwg_embed.h
 
 
 def _as_ids(x):
@@ -112,6 +112,13 @@ class DiscreteSymbolHiFiGANGenerator(HiFiGANGenerator):
         return self.num_spk_embs <= 0 and self.use_embedding_feats
 
     # ------------------------------------------------------------------ engine plumbing
+    _front_prefixes = ("emb.", "spk_emb.")  # state-dict keys of the front end: not part of the body program
+
+    def _load_front(self, dev):
+        """The front end's fp32 device tensors, refreshed whenever the body's packed image is."""
+        spk = self.spk_emb.weight.detach().to(dev, torch.float32).contiguous() if self.num_spk_embs > 0 else None
+        self._tables = (self.emb.weight.detach().to(dev, torch.float32).contiguous(), spk)
+
     def _device(self):
         dev = first_parameter(self).device
         if dev.type != "cuda":
@@ -126,10 +133,9 @@ class DiscreteSymbolHiFiGANGenerator(HiFiGANGenerator):
             self._weights.invalidate()
         if self._weights.changed(self):
             with torch.no_grad():
-                state = {k: v for k, v in self.state_dict().items() if not k.startswith(("emb.", "spk_emb."))}
+                state = {k: v for k, v in self.state_dict().items() if not k.startswith(self._front_prefixes)}
                 self._engine.load_state_dict(state)
-                spk = self.spk_emb.weight.detach().to(dev, torch.float32).contiguous() if self.num_spk_embs > 0 else None
-                self._tables = (self.emb.weight.detach().to(dev, torch.float32).contiguous(), spk)
+                self._load_front(dev)
             if self._flag is None or self._flag.device != dev:
                 self._flag = torch.zeros(1, dtype=torch.int32, device=dev)
                 self._flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
@@ -205,22 +211,30 @@ class DiscreteSymbolHiFiGANGenerator(HiFiGANGenerator):
                 self.num_spk_embs if spk is not None else 0, dim, ids_d.data_ptr(),
                 spk_d.data_ptr() if spk_d is not None else None, rs_d.data_ptr(), n, rows, feats.data_ptr(),
                 self._flag.data_ptr(), stream.cuda_stream))
-            # the flag travels to pinned memory on the same stream, ahead of the forward: by the time
-            # CnetEngine.run(check=True) has synchronised for its range status the copy has landed, and
-            # the success path pays no synchronisation of its own
-            self._flag_host.copy_(self._flag, non_blocking=True)
-            self._flag_event.record(stream)
+            self._flag_fetch(stream)
             outs = eng.infer_rows(frames, feats)
-            if not self._flag_event.query():  # (exact-fp32 mode: run() has no status to wait for)
-                self._flag_event.synchronize()
-            self._stage_busy = False
-            bits = int(self._flag_host[0])
-            if bits:
-                self._flag.zero_()
-                what = [w for b, w in ((BAD_TOKEN, f"a token id outside [0, {self.num_embs})"),
-                                       (BAD_SPEAKER, f"a speaker id outside [0, {self.num_spk_embs})")) if bits & b]
-                raise IndexError("the batch holds " + " and ".join(what))
+            self._flag_raise()
         return outs
+
+    def _flag_fetch(self, stream):
+        """The flag travels to pinned memory on the same stream, ahead of the forward: by the time
+        CnetEngine.run(check=True) has synchronised for its range status the copy has landed, and
+        the success path pays no synchronisation of its own."""
+        self._flag_host.copy_(self._flag, non_blocking=True)
+        self._flag_event.record(stream)
+
+    def _flag_raise(self):
+        if not self._flag_event.query():  # (exact-fp32 mode: run() has no status to wait for)
+            self._flag_event.synchronize()
+        self._stage_busy = False
+        bits = int(self._flag_host[0])
+        if bits:
+            self._flag.zero_()
+            what = [w for b, w in ((BAD_TOKEN, f"a token id outside [0, {self.num_embs})"),
+                                   (BAD_SPEAKER, f"a speaker id outside [0, {self.num_spk_embs})"),
+                                   (BAD_DURATION, "a duration outside [0, 2^31)")) if bits & b]
+            # (ids are IndexError as in torch.nn.Embedding; a bad duration alone is a ValueError)
+            raise (IndexError if bits & (BAD_TOKEN | BAD_SPEAKER) else ValueError)("the batch holds " + " and ".join(what))
 
     def _want_columns(self):
         return 2 if self.num_spk_embs > 0 else 1

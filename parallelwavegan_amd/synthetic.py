@@ -118,7 +118,8 @@ def make_module_state_dict(module, seed=0, gain=1.0, bias_std=0.05, weight_norm=
     ~ N(0, gain^2 / fan_in) with fan_in = C_in*K (Conv1d) or C_in*2 (ConvTranspose1d, 2 taps per
     output), biases ~ N(0, bias_std^2). Keys follow the module's state dict: with weight norm
     applied, ``weight_v`` = the drawn weight and ``weight_g`` = ||v|| * U(0.5, 1.5) per output
-    slice. Embedding tables ~ N(0, 1) (torch.nn.Embedding's initialisation). Buffers (PQMF filters,
+    slice. Embedding tables ~ N(0, 1) (torch.nn.Embedding's initialisation), Linear weights like conv
+    weights with fan_in = in_features, LayerNorm weights ~ N(1, 0.1^2), bare parameters ~ N(1, 0.5^2). Buffers (PQMF filters,
     stats) are left out."""
     import torch
 
@@ -132,10 +133,19 @@ def make_module_state_dict(module, seed=0, gain=1.0, bias_std=0.05, weight_norm=
             kinds[name] = ("conv", m.in_channels * m.kernel_size[0])
         elif isinstance(m, torch.nn.Embedding):
             kinds[name] = ("emb", 1)
+        elif isinstance(m, torch.nn.Linear):
+            kinds[name] = ("linear", m.in_features)
+        elif isinstance(m, torch.nn.LayerNorm):
+            kinds[name] = ("norm", 1)
     for key, p in module.named_parameters():
-        base, leaf = key.rsplit(".", 1)
         shape = tuple(p.shape)
-        if leaf == "bias":
+        if "." not in key:  # a bare parameter of the module (the weighted-sum ``weights``)
+            sd[key] = (1.0 + 0.5 * rs.standard_normal(shape)).astype(np.float32)
+            continue
+        base, leaf = key.rsplit(".", 1)
+        if leaf == "weight" and kinds[base][0] == "norm":
+            sd[key] = (1.0 + 0.1 * rs.standard_normal(shape)).astype(np.float32)
+        elif leaf == "bias":
             sd[key] = (bias_std * rs.standard_normal(shape)).astype(np.float32)
         elif leaf in ("weight", "weight_v"):
             kind, fan = kinds[base]

@@ -18,18 +18,22 @@ import numpy as np
 import torch
 import yaml
 
-GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator", "DiscreteSymbolHiFiGANGenerator")
+GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator", "DiscreteSymbolHiFiGANGenerator",
+              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator")
 
 
 def generator_class(name):
     from .dsym import DiscreteSymbolHiFiGANGenerator
+    from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator
     from .hifigan import HiFiGANGenerator
     from .melgan import MelGANGenerator
     from .models import ParallelWaveGANGenerator
 
     table = {"ParallelWaveGANGenerator": ParallelWaveGANGenerator, "MelGANGenerator": MelGANGenerator,
              "HiFiGANGenerator": HiFiGANGenerator,
-             "DiscreteSymbolHiFiGANGenerator": DiscreteSymbolHiFiGANGenerator}
+             "DiscreteSymbolHiFiGANGenerator": DiscreteSymbolHiFiGANGenerator,
+             "DiscreteSymbolDurationGenerator": DiscreteSymbolDurationGenerator,
+             "DiscreteSymbolF0Generator": DiscreteSymbolF0Generator}
     if name not in table:
         raise NotImplementedError(f"generator_type {name!r} is not accelerated (supported: {', '.join(GENERATORS)})")
     return table[name]
