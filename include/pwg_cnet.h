@@ -26,6 +26,17 @@
  * (layers/causal_conv.py:43-78: ReplicationPad1d((1, 0)), ConvTranspose1d, trim stride on both
  * sides), i.e. y[q*s + r] = W[:, :, r] x[q] + W[:, :, r + s] x[max(q - 1, 0)].
  * PWG_CNET_PQMF is PQMF.synthesis (layers/pqmf.py:133-149) with host-supplied filters.
+ * A PWG_CNET_CONVT with src[1].buf >= 0 runs over the channel concatenation [src[0]; src[1]] of two
+ * buffers of one rate (UHiFiGAN's torch.cat + ConvTranspose1d, models/uhifigan.py:290-291): rows
+ * [0, C0) of the one weight tensor at src[0].w_off belong to src[0], [C0, C0 + C1) to src[1]
+ * (src[1].w_off is not used); each source has its own pre_slope. Zero-padded, one launch on the
+ * tap-major kernel.
+ * PWG_CNET_SCONV is the strided Conv1d(kernel 2*stride, stride, padding) of UHiFiGAN's encoder
+ * (models/uhifigan.py:118-135): y[o, q] = post(b[o] + sum W[o, i, k] pre(x[i, q*stride - padding + k]))
+ * from a buffer of `stride` times the destination's rate, zero taps outside the utterance. It uses
+ * src[0] (taps = 2*stride, dilation 1, channels a multiple of 16), `stride` (2..8), `padding`,
+ * b_off, post_act / post_slope; no residual, accumulate, division or second source, and it cannot
+ * write the program output. Anything else is PWG_ERR_UNSUPPORTED.
  *
  * Buffers are time-major [rows][ld] fp32 (ld = channels rounded up to 16); buffer b of a plan
  * holds frames[u] * rate[b] rows per utterance u, utterances back to back. Buffer 0 is the input
@@ -44,7 +55,7 @@ extern "C" {
 
 #define PWG_CNET_ABI_VERSION 1
 
-enum { PWG_CNET_CONV = 0, PWG_CNET_CONVT = 1, PWG_CNET_PQMF = 2 };
+enum { PWG_CNET_CONV = 0, PWG_CNET_CONVT = 1, PWG_CNET_PQMF = 2, PWG_CNET_SCONV = 3 };
 enum { PWG_PAD_ZERO = 0, PWG_PAD_REFLECT = 1, PWG_PAD_REPLICATE = 2 };
 enum { PWG_ACT_NONE = 0, PWG_ACT_LRELU = 1, PWG_ACT_TANH = 2 };
 
@@ -65,7 +76,7 @@ typedef struct PwgCnetOp {
   int kind;           /* PWG_CNET_* */
   int dst;            /* output buffer id */
   int out_channels;
-  PwgCnetSrc src[2];  /* CONVT and PQMF use src[0] only */
+  PwgCnetSrc src[2];  /* PQMF and SCONV use src[0] only; CONVT uses src[1] when its buf >= 0 */
   long long b_off;    /* bias (out_channels floats) or -1 */
   long long b2_off;   /* second bias summed with the first (two-source ops) or -1 */
   int res;            /* buffer added after the bias, -1 = none */
@@ -73,8 +84,9 @@ typedef struct PwgCnetOp {
   float out_div;      /* result divided by this (1.0 = none) */
   int post_act;       /* PWG_ACT_* */
   float post_slope;
-  int stride;         /* CONVT: stride (rate[dst] = stride * rate[src]); PQMF: subbands */
-  int padding;        /* CONVT: padding; PQMF: filter taps (odd, = taps+1 of PQMF) */
+  int stride;         /* CONVT: stride (rate[dst] = stride * rate[src]); PQMF: subbands;
+                         SCONV: stride (rate[src] = stride * rate[dst]) */
+  int padding;        /* CONVT, SCONV: padding; PQMF: filter taps (odd, = taps+1 of PQMF) */
   int output_padding; /* CONVT */
 } PwgCnetOp;
 
@@ -104,11 +116,25 @@ PWG_API int pwg_cnet_plan_image(const PwgCnetPlan* p, long long* offset_bytes, l
                                 long long cap);
 PWG_API long long pwg_cnet_plan_rows(const PwgCnetPlan* p, int buf); /* sum_u frames[u]*rate[buf] */
 PWG_API long long pwg_cnet_plan_workspace_bytes(const PwgCnetPlan* p);
+/* Where an internal buffer lives in the workspace: its byte offset, rows and row stride in floats
+ * (the input, the output and an external buffer are the caller's: PWG_ERR_INVALID). Buffers whose
+ * live ranges do not overlap share storage unless the plan's launches run concurrently
+ * (PWG_CNET_OPT_STREAMS 2 gives every buffer its own slot). For tests and tools. */
+PWG_API int pwg_cnet_plan_buffer(const PwgCnetPlan* p, int buf, long long* offset_bytes, long long* rows, int* ld);
 /* mel: buffer 0 contents (device, rows x channels[0], frames-major = time-major);
  * out: the last buffer's first channels[last] channels, time-major (device);
  * mean/scale: device or NULL (ops with normalize=1 need them). */
 PWG_API int pwg_cnet_run(PwgCnetPlan* p, const float* packed, const float* mel, const float* mean,
                  const float* scale, float* out, void* workspace, void* stream);
+/* One external buffer besides buffer 0: an internal buffer (1 .. n_bufs - 2) with no writer and a
+ * multiple of 16 channels whose rows (packed rows x channels fp32, frames[u] * rate[buf] per
+ * utterance) the caller supplies to every run -- UHiFiGAN's excitation features at the sample rate,
+ * written by pwg_uhg_excite_rows (include/pwg_uhg.h). Call before the handle's first plan; the
+ * buffer then takes no workspace. pwg_cnet_run_ext is pwg_cnet_run plus that device pointer;
+ * pwg_cnet_run refuses a program with an external buffer, pwg_cnet_run_ext one without. */
+PWG_API int pwg_cnet_set_external(PwgCnet* n, int buf);
+PWG_API int pwg_cnet_run_ext(PwgCnetPlan* p, const float* packed, const float* mel, const float* mean,
+                             const float* scale, const float* ext, float* out, void* workspace, void* stream);
 /* Split-f16 range status of the last pwg_cnet_run on this workspace (synchronises `stream`):
  * PWG_ERR_RANGE when the program output holds a non-finite value, i.e. some activation left the
  * fp16 pair range upstream (it became (inf, -inf), every later product NaN) or the input was not

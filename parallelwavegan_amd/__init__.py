@@ -10,6 +10,8 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
                             its duration- and f0-conditioned siblings (HIP duration predictor, length
                             regulator and f0 / weighted-sum front ends)
   StyleMelGANGenerator      drop-in StyleMelGAN generator on the TADE kernels (include/pwg_smg.h)
+  UHiFiGANGenerator         drop-in U-Net HiFiGAN (mel + excitation): HIP excitation front end, strided
+                            and two-source transposed convs on the conv-network executor
 """
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
@@ -17,5 +19,6 @@ from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
 from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator  # noqa: F401
 from .models import ParallelWaveGANGenerator  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401
+from .uhifigan import UHiFiGANGenerator  # noqa: F401
 
 __version__ = "0.1.0"

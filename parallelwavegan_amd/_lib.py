@@ -30,12 +30,14 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_embed.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_embed_ext.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_smg.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_uconv.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
     os.path.join(REPO_DIR, "include", "pwg_cnet.h"),
     os.path.join(REPO_DIR, "include", "pwg_embed.h"),
     os.path.join(REPO_DIR, "include", "pwg_smg.h"),
+    os.path.join(REPO_DIR, "include", "pwg_uhg.h"),
     os.path.join(PKG_DIR, "csrc", "pwg_internal.h"),
 ]
 OFFLOAD_ARCH = "gfx950"
@@ -98,7 +100,10 @@ EXPORTED_SYMBOLS = (
     "pwg_cnet_plan_image",
     "pwg_cnet_plan_rows",
     "pwg_cnet_plan_workspace_bytes",
+    "pwg_cnet_plan_buffer",
     "pwg_cnet_run",
+    "pwg_cnet_set_external",
+    "pwg_cnet_run_ext",
     "pwg_cnet_run_status",
     "pwg_cnet_plan_schedule",
     "pwg_cnet_set_option",
@@ -115,6 +120,8 @@ EXPORTED_SYMBOLS = (
     "pwg_regulate_scan",
     "pwg_regulate_rows",
     "pwg_embed_rows_f0",
+    # include/pwg_uhg.h: UHiFiGAN's excitation front end (csrc/pwg_uconv.hip)
+    "pwg_uhg_excite_rows",
     # include/pwg_smg.h: StyleMelGAN generator path
     "pwg_smg_create",
     "pwg_smg_destroy",
@@ -387,6 +394,7 @@ def load():
         lib.pwg_regulate_scan.argtypes = [vp, vp, ci, ll, vp, vp, vp, vp]
         lib.pwg_regulate_rows.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, ll, ll, vp, vp, vp]
         lib.pwg_embed_rows_f0.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ll, vp, vp, vp]
+        lib.pwg_uhg_excite_rows.argtypes = [vp, vp, vp, ci, ci, ctypes.c_float, vp, ci, ll, vp, vp]
         lib.pwg_smg_create.argtypes = [ctypes.POINTER(PwgSmgConfig), ctypes.c_int, ctypes.POINTER(vp)]
         lib.pwg_smg_destroy.argtypes = [vp]
         lib.pwg_smg_destroy.restype = None

@@ -17,7 +17,10 @@ Same arguments for the mel-to-wave case (--dumpdir with ``*-feats.npy`` files, -
   * DiscreteSymbolDurationGenerator decodes in three steps: the durations of a batch of token
     sequences are predicted (predict_durations), the engine passes are then sized by the regulated
     frame counts instead of the token counts, and the tokens are decoded with ``ds=`` (host-resident
-    durations: no further device-to-host traffic).
+    durations: no further device-to-host traffic);
+  * UHiFiGANGenerator reads ``*-excitation.npy`` beside each ``*-feats.npy`` (bin/decode.py:188-192 of
+    the reference) and fails before any decoding when one is missing; ``*-f0.npy`` is read if present
+    and otherwise ignored (the generator never uses f0, models/uhifigan.py:261-301).
 """
 
 import argparse
@@ -52,10 +55,24 @@ def batch_cost_model(model, device, frac=0.25, cap_gib=8.0, probe_frames=512, pr
     one = eng.plan([probe_frames]).workspace_bytes
     many = eng.plan([probe_frames // probe_utts] * probe_utts).workspace_bytes
     per_frame = one / probe_frames + 4 * in_ch + 4 * hop * (out_ch + noise)
+    ext = getattr(getattr(eng, "program", None), "external", -1)
+    if ext >= 0:  # UHiFiGAN: the excitation samples and the front end's rows (the external buffer)
+        per_frame += 4 * eng.program.rate[ext] * (1 + eng.program.channels[ext])
     per_utt = max(0.0, (many - one) / (probe_utts - 1))
     free, _ = torch.cuda.mem_get_info(device)
     budget = min(free * frac, cap_gib * (1 << 30))
     return per_frame, per_utt, budget
+
+
+def excitation_files(feats_files):
+    """The ``*-excitation.npy`` file beside each ``*-feats.npy`` (UHiFiGANGenerator); raises
+    FileNotFoundError naming the first utterances that lack one."""
+    paths = [f[:-len("-feats.npy")] + "-excitation.npy" for f in feats_files]
+    missing = [p for p in paths if not os.path.exists(p)]
+    if missing:
+        raise FileNotFoundError(f"UHiFiGANGenerator needs an excitation dump beside every feature file: "
+                                f"{len(missing)} missing, first {missing[0]}")
+    return paths
 
 
 def main(argv=None):
@@ -92,6 +109,9 @@ def main(argv=None):
     config.update(vars(args))
     if config.get("format", "npy") != "npy":
         raise NotImplementedError("hdf5 dumps need h5py, which is not available; dump with format: npy")
+
+    uhifigan = config.get("generator_type") == "UHiFiGANGenerator"
+    exc_files = excitation_files(find_files(args.dumpdir, "*-feats.npy")) if uhifigan else None
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = 0
@@ -181,9 +201,19 @@ def main(argv=None):
                                  for _, i in batch]
             if with_durations:
                 kwargs["ds"] = [durations[i] for _, i in batch]
+            if uhifigan:
+                excs = [np.ascontiguousarray(np.load(exc_files[i], allow_pickle=False), np.float32).reshape(-1)
+                        for _, i in batch]
+                for _, i in batch:  # read like the reference does, never used by the generator
+                    f0_path = files[i].replace("-feats.npy", "-f0.npy")
+                    if os.path.exists(f0_path):
+                        np.load(f0_path, allow_pickle=False)
             start = time.time()
             with torch.no_grad():
-                ys = model.inference_batch(cs, normalize_before=args.normalize_before, **kwargs)
+                if uhifigan:
+                    ys = model.inference_batch(cs, excs)
+                else:
+                    ys = model.inference_batch(cs, normalize_before=args.normalize_before, **kwargs)
                 ys = [y.view(-1).cpu().numpy() for y in ys]
             el = time.time() - start + sum(predict_time.get(i, 0.0) for _, i in batch)
             audio = sum(len(y) for y in ys) / sr

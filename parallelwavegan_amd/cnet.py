@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .engine import fold_weight_norm
 
-CONV, CONVT, PQMF = 0, 1, 2
+CONV, CONVT, PQMF, SCONV = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT, PAD_REPLICATE = 0, 1, 2
 ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
 
@@ -85,7 +85,11 @@ def lib():
         L.pwg_cnet_plan_rows.restype = ll
         L.pwg_cnet_plan_workspace_bytes.argtypes = [vp]
         L.pwg_cnet_plan_workspace_bytes.restype = ll
+        L.pwg_cnet_plan_buffer.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ll), ctypes.POINTER(ll),
+                                           ctypes.POINTER(ctypes.c_int)]
         L.pwg_cnet_run.argtypes = [vp] * 8
+        L.pwg_cnet_run_ext.argtypes = [vp] * 9
+        L.pwg_cnet_set_external.argtypes = [vp, ctypes.c_int]
         L.pwg_cnet_run_status.argtypes = [vp, vp, vp]
         ip = ctypes.POINTER(ctypes.c_int)
         L.pwg_cnet_plan_schedule.argtypes = [vp, ctypes.c_int, ip, ip, ip, ip]
@@ -110,11 +114,20 @@ class Program:
         self.ops = []
         self.names = []
         self.weights = OrderedDict()  # key -> number of floats
+        self.external = -1  # buffer the caller supplies to every run (pwg_cnet_set_external), -1 none
 
     def buffer(self, channels, rate):
         self.channels.append(int(channels))
         self.rate.append(int(rate))
         return len(self.channels) - 1
+
+    def external_buffer(self, channels, rate):
+        """A buffer with no writer whose rows the caller passes to every run (one per program):
+        UHiFiGAN's excitation features, written by the front-end kernel."""
+        if self.external >= 0:
+            raise ValueError("a program has one external buffer at most")
+        self.external = self.buffer(channels, rate)
+        return self.external
 
     def _w(self, key, count):
         if key is None:
@@ -143,12 +156,26 @@ class Program:
                              post_slope=post_slope, stride=1, padding=0, output_padding=0))
         self.names.append(name)
 
-    def convt(self, name, dst, out_channels, src, stride, padding, output_padding, bias=None):
-        self._w(src["weight"], src["channels"] * out_channels * 2 * stride)
+    def convt(self, name, dst, out_channels, src, stride, padding, output_padding, bias=None, src2=None):
+        """ConvTranspose1d(kernel 2 * stride); with ``src2`` over the channel concatenation
+        [src; src2], both reading rows of the one weight tensor ``src["weight"]``."""
+        cin = src["channels"] + (src2["channels"] if src2 is not None else 0)
+        self._w(src["weight"], cin * out_channels * 2 * stride)
         self._w(bias, out_channels)
-        self.ops.append(dict(kind=CONVT, dst=dst, out_channels=out_channels, srcs=[src], bias=bias, bias2=None,
+        srcs = [src] if src2 is None else [src, dict(src2, weight=None)]
+        self.ops.append(dict(kind=CONVT, dst=dst, out_channels=out_channels, srcs=srcs, bias=bias, bias2=None,
                              res=-1, accumulate=False, out_div=1.0, post_act=ACT_NONE, post_slope=1.0,
                              stride=stride, padding=padding, output_padding=output_padding))
+        self.names.append(name)
+
+    def sconv(self, name, dst, out_channels, src, stride, padding, bias=None, post_act=ACT_NONE, post_slope=1.0):
+        """Strided Conv1d(kernel 2 * stride, stride, padding): ``src`` has ``stride`` times the
+        rate of ``dst`` (PWG_CNET_SCONV)."""
+        self._w(src["weight"], out_channels * src["channels"] * src["taps"])
+        self._w(bias, out_channels)
+        self.ops.append(dict(kind=SCONV, dst=dst, out_channels=out_channels, srcs=[src], bias=bias, bias2=None,
+                             res=-1, accumulate=False, out_div=1.0, post_act=post_act, post_slope=post_slope,
+                             stride=stride, padding=padding, output_padding=0))
         self.names.append(name)
 
     def pqmf(self, name, dst, src_buf, subbands, filt_key, filt_taps):
@@ -230,6 +257,13 @@ class CnetPlan:
                                                      img.ctypes.data, n.value))
         return off.value, img
 
+    def buffer(self, buf):
+        """pwg_cnet_plan_buffer: (byte offset in the workspace, rows, row stride in floats)."""
+        off, rows, ld = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_int()
+        _lib.check(self.eng._lib.pwg_cnet_plan_buffer(self._p, buf, ctypes.byref(off), ctypes.byref(rows),
+                                                      ctypes.byref(ld)))
+        return off.value, rows.value, ld.value
+
     def __del__(self):
         p = getattr(self, "_p", None)
         h = getattr(self.eng, "_h", None)
@@ -261,6 +295,8 @@ class CnetEngine:
         h = ctypes.c_void_p()
         _lib.check(L.pwg_cnet_create(ops, len(program.ops), nb, ch, rt, n_ref, idx, ctypes.byref(h)))
         self._h = h
+        if program.external >= 0:
+            _lib.check(L.pwg_cnet_set_external(h, program.external))
         self.packed_weight_count = L.pwg_cnet_packed_weight_count(h)
         self.packed = None
         self._plans = OrderedDict()
@@ -381,13 +417,14 @@ class CnetEngine:
     def hop(self):
         return self.program.rate[-1]
 
-    def run(self, plan, mel, out, mean=None, scale=None, stream=None, check=True):
+    def run(self, plan, mel, out, mean=None, scale=None, stream=None, check=True, ext=None):
         """Enqueue one forward of ``plan`` on ``stream`` (default: torch's current stream).
 
         check=True (the drop-ins' setting) reads the split-f16 range status after the forward
         (pwg_cnet_run_status: one stream synchronisation) and, when the output came out non-finite,
         redoes the forward in exact fp32, so the result always holds the reference's fp32
-        semantics. check=False only enqueues (the bench's timed loop; ``run_status`` afterwards)."""
+        semantics. check=False only enqueues (the bench's timed loop; ``run_status`` afterwards).
+        ``ext``: the rows of the program's external buffer (pwg_cnet_run_ext), if it has one."""
         if stream is None:
             stream = torch.cuda.current_stream(self.device)
         ws = None
@@ -403,7 +440,7 @@ class CnetEngine:
             self._last_ws[key] = ws  # run_status reads the captured forward's own workspace
         else:
             self._last_ws.pop(key, None)
-            self._enqueue(plan, mel, out, mean, scale, stream)
+            self._enqueue(plan, mel, out, mean, scale, stream, ext=ext)
         if check and self.split_f16:
             try:
                 if ws is None:
@@ -414,7 +451,7 @@ class CnetEngine:
                 logging.warning("%s; rerunning in exact fp32", e)
                 self._set_split(False)
                 try:
-                    self._enqueue(plan, mel, out, mean, scale, stream)
+                    self._enqueue(plan, mel, out, mean, scale, stream, ext=ext)
                 finally:
                     self._set_split(True)
                 self.range_reruns += 1
@@ -445,7 +482,8 @@ class CnetEngine:
         self._graphs.clear()
 
     def _graph_ok(self, plan, mean, stream, uses):
-        return (self.graphs and self._branchy and not self._timing and mean is None
+        # (a program with an external buffer runs eagerly: the captured forward carries buffer 0 only)
+        return (self.graphs and self._branchy and not self._timing and mean is None and self.program.external < 0
                 and sum(plan.frames) <= self.GRAPH_MAX_FRAMES and not torch.cuda.is_current_stream_capturing()
                 and (uses >= self.GRAPH_AFTER or self._graph_key(plan, stream) in self._graphs))
 
@@ -508,7 +546,7 @@ class CnetEngine:
             ws = self.workspace(plan.workspace_bytes, stream)
         _lib.check(self._lib.pwg_cnet_run_status(plan._p, ws.data_ptr(), stream.cuda_stream))
 
-    def _enqueue(self, plan, mel, out, mean, scale, stream, ws=None):
+    def _enqueue(self, plan, mel, out, mean, scale, stream, ws=None, ext=None):
         if self.packed is None:
             raise RuntimeError("no weights loaded")
         for name, t in (("mel", mel), ("out", out)):
@@ -525,6 +563,19 @@ class CnetEngine:
             mp, sp = mean.data_ptr(), scale.data_ptr()
         if ws is None:
             ws = self.workspace(plan.workspace_bytes, stream)
+        eb = self.program.external
+        if eb >= 0:
+            if ext is None:
+                raise ValueError("the program has an external buffer: pass its rows as ext")
+            if ext.device != self.device or ext.dtype != torch.float32 or not ext.is_contiguous():
+                raise ValueError(f"ext must be a contiguous float32 tensor on {self.device}")
+            if ext.numel() != sum(plan.frames) * self.program.rate[eb] * self.program.channels[eb]:
+                raise ValueError("ext has the wrong size for the plan")
+            _lib.check(self._lib.pwg_cnet_run_ext(plan._p, self.packed.data_ptr(), mel.data_ptr(), mp, sp,
+                                                  ext.data_ptr(), out.data_ptr(), ws.data_ptr(), stream.cuda_stream))
+            return out
+        if ext is not None:
+            raise ValueError("the program has no external buffer")
         _lib.check(self._lib.pwg_cnet_run(plan._p, self.packed.data_ptr(), mel.data_ptr(), mp, sp, out.data_ptr(),
                                           ws.data_ptr(), stream.cuda_stream))
         return out
@@ -535,13 +586,13 @@ class CnetEngine:
         mel = torch.cat([m.reshape(-1) for m in mels]) if len(mels) > 1 else mels[0].reshape(-1).contiguous()
         return self.infer_rows(frames, mel, mean, scale)
 
-    def infer_rows(self, frames, mel, mean=None, scale=None):
+    def infer_rows(self, frames, mel, mean=None, scale=None, ext=None):
         """``infer`` for input rows that are already packed: ``mel`` holds sum(frames) x in_channels
         floats, utterances back to back (what a front-end kernel wrote)."""
         plan = self.plan(frames)
         O = self.out_channels
         out = torch.empty(plan.out_rows * O, dtype=torch.float32, device=self.device)
-        self.run(plan, mel, out, mean, scale)
+        self.run(plan, mel, out, mean, scale, ext=ext)
         res, off = [], 0
         for f in frames:
             T = f * self.hop

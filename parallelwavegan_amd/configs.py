@@ -233,3 +233,38 @@ def style_melgan_params(name, **overrides):
     p = copy.deepcopy(STYLE_MELGAN_PARAMS[name])
     p.update(copy.deepcopy(overrides))
     return p
+
+
+# UHiFiGAN generators (models/uhifigan.py:19-387), a table of their own: they take an excitation
+# signal besides the mel, and the MelGAN-family tests iterate VOCODER_PARAMS.
+#   uhifigan_v1  egs/{opencpop,opensinger}/voc1/conf/uhifigan.v1.yaml (24 kHz singing, hop 300)
+# ``*_test`` are reduced shapes: odd and even scales with two residual-block shapes, and a variant
+# without additional convs or biases.
+UHIFIGAN_PARAMS = {
+    "uhifigan_v1": dict(in_channels=80, out_channels=1, channels=32, kernel_size=7,
+                        downsample_scales=[5, 5, 4, 3], downsample_kernel_sizes=[10, 10, 8, 6],
+                        upsample_scales=[3, 4, 5, 5], upsample_kernel_sizes=[6, 8, 10, 10],
+                        resblock_kernel_sizes=[3, 7, 11], resblock_dilations=[[1, 3, 5], [1, 3, 5], [1, 3, 5]],
+                        dropout=0.1, use_additional_convs=True, bias=True, nonlinear_activation="LeakyReLU",
+                        nonlinear_activation_params={"negative_slope": 0.1}, use_weight_norm=True),
+    "uhifigan_test": dict(in_channels=80, out_channels=1, channels=32, kernel_size=7,
+                          downsample_scales=[3, 2, 2], downsample_kernel_sizes=[6, 4, 4],
+                          upsample_scales=[2, 2, 3], upsample_kernel_sizes=[4, 4, 6],
+                          resblock_kernel_sizes=[3, 5], resblock_dilations=[[1, 3], [1, 2]],
+                          dropout=0.1, use_additional_convs=True, bias=True, nonlinear_activation="LeakyReLU",
+                          nonlinear_activation_params={"negative_slope": 0.1}, use_weight_norm=True),
+    "uhifigan_noadd_nobias_test": dict(in_channels=16, out_channels=1, channels=32, kernel_size=5,
+                                       downsample_scales=[5, 4], downsample_kernel_sizes=[10, 8],
+                                       upsample_scales=[4, 5], upsample_kernel_sizes=[8, 10],
+                                       resblock_kernel_sizes=[3], resblock_dilations=[[1, 2]],
+                                       dropout=0.1, use_additional_convs=False, bias=False,
+                                       nonlinear_activation="LeakyReLU",
+                                       nonlinear_activation_params={"negative_slope": 0.1}, use_weight_norm=True),
+}
+
+
+def uhifigan_params(name, **overrides):
+    """Deep-copied UHiFiGANGenerator constructor arguments of a recipe."""
+    p = copy.deepcopy(UHIFIGAN_PARAMS[name])
+    p.update(copy.deepcopy(overrides))
+    return p

@@ -3484,6 +3484,7 @@ struct OpPhase {          // one launch
   int rconv_mt = 0;           // > 0: a k = 3 x-tile conv of 32 rconv_mt channels that pwg_rconv_kernel runs
   int ms_n = 0;               // > 0: head of a chain of this many fusable ResidualStacks (pwg_mstack.hip)
   int ms_halo = 0;            // ... their summed dilations
+  bool sconv = false;         // PWG_CNET_SCONV: pwg_uconv.hip's strided conv (chunks channel-block-major)
 };
 
 }  // namespace
@@ -3525,6 +3526,8 @@ struct PwgCnet {
   bool pair_attr_set = false;
   std::vector<PwgCnetOp> ops;
   std::vector<int> channels, rate, ld;
+  int ext_buf = -1;    // pwg_cnet_set_external: the buffer pwg_cnet_run_ext's caller supplies (-1 none)
+  bool planned = false;  // a plan was created: the program's buffers are fixed
   long long ref_count = 0;
   std::vector<OpPhase> phases;
   long long packed_count = 0;
@@ -3706,13 +3709,15 @@ int cnet_schedule(PwgCnetPlan* p, CnSchedule& sc) {
     int tail[1 + PwgCnet::N_AUX] = {-1, -1, -1, -1}, used_at[1 + PwgCnet::N_AUX] = {-1, -1, -1, -1};
     for (size_t L = 0; L < launches.size(); ++L) {
       std::vector<int> deps;
+      bool ext_read = false;  // reads the external buffer (ready before the run: no writer to follow)
       auto op_deps = [&](int oi) {
         const PwgCnetOp& o = n->ops[oi];
         auto rd = [&](int b) {
           if (b >= 0 && last_writer[mem[b]] >= 0) deps.push_back(last_writer[mem[b]]);
+          ext_read |= b >= 0 && b == n->ext_buf;
         };
         rd(o.src[0].buf);
-        if (o.kind == PWG_CNET_CONV) rd(o.src[1].buf);
+        if (o.kind == PWG_CNET_CONV || o.kind == PWG_CNET_CONVT) rd(o.src[1].buf);
         rd(o.res);
         if (o.accumulate) rd(o.dst);
         if (last_writer[mem[o.dst]] >= 0) deps.push_back(last_writer[mem[o.dst]]);  // WAW
@@ -3726,9 +3731,11 @@ int cnet_schedule(PwgCnetPlan* p, CnSchedule& sc) {
       int st;
       if (best >= 0) {
         st = l_stream[best];
-      } else if (deps.empty()) {
+      } else if (deps.empty() && !ext_read) {
         st = 0;
       } else {
+        // (also the heads of parallel branches that start at the external buffer -- the residual
+        // blocks of UHiFiGAN's first encoder stage: nothing to follow, so each takes its own stream)
         st = 0;
         for (int k = 1; k < NS; ++k)
           if (used_at[k] < used_at[st]) st = k;
@@ -3742,7 +3749,8 @@ int cnet_schedule(PwgCnetPlan* p, CnSchedule& sc) {
       stream_used[st] = true;
       auto note = [&](int oi) {
         const PwgCnetOp& o = n->ops[oi];
-        for (int b : {o.src[0].buf, o.kind == PWG_CNET_CONV ? o.src[1].buf : -1, o.res, o.accumulate ? o.dst : -1})
+        for (int b : {o.src[0].buf, o.kind == PWG_CNET_CONV || o.kind == PWG_CNET_CONVT ? o.src[1].buf : -1, o.res,
+                      o.accumulate ? o.dst : -1})
           if (b >= 0) readers[mem[b]].push_back((int)L);
       };
       note(n->phases[launches[L].first].op);
@@ -3812,8 +3820,10 @@ float ref_weight(const PwgCnetOp& op, const OpPhase& ph, const float* ref, int s
   if (o >= op.out_channels || i >= src.channels) return 0.f;
   if (op.kind == PWG_CNET_CONVT) {
     // ConvTranspose1d weight (C_in, C_out, 2*stride); phase tap k=0 -> k_a, k=1 -> k_a + stride
+    // (two sources: rows [0, C0) of the one weight tensor are src[0]'s, [C0, C0 + C1) src[1]'s)
     const int kk = ph.k_a + k * op.stride;
-    return ref[src.w_off + ((long long)i * op.out_channels + o) * (2 * op.stride) + kk];
+    const long long row = i + (s == 1 ? op.src[0].channels : 0);
+    return ref[op.src[0].w_off + (row * op.out_channels + o) * (2 * op.stride) + kk];
   }
   return ref[src.w_off + ((long long)o * src.channels + i) * src.taps + k];
 }
@@ -3865,8 +3875,12 @@ int pwg_cnet_create(const PwgCnetOp* ops, int n_ops, int n_bufs, const int* chan
       n->phases.push_back(ph);
       continue;
     }
-    if (op.kind != PWG_CNET_CONV && op.kind != PWG_CNET_CONVT) { delete n; return fail(PWG_ERR_INVALID, where + "bad kind"); }
-    const int nsrc = (op.src[1].buf >= 0 && op.kind == PWG_CNET_CONV) ? 2 : 1;
+    if (op.kind != PWG_CNET_CONV && op.kind != PWG_CNET_CONVT && op.kind != PWG_CNET_SCONV) {
+      delete n;
+      return fail(PWG_ERR_INVALID, where + "bad kind");
+    }
+    const bool sconv = op.kind == PWG_CNET_SCONV;
+    const int nsrc = (op.src[1].buf >= 0 && !sconv) ? 2 : 1;
     for (int s = 0; s < nsrc; ++s) {
       const PwgCnetSrc& src = op.src[s];
       if (src.buf < 0 || src.buf >= n_bufs || src.channels < 1 || src.channels > channels[src.buf] || src.taps < 1 ||
@@ -3891,6 +3905,21 @@ int pwg_cnet_create(const PwgCnetOp* ops, int n_ops, int n_bufs, const int* chan
       return fail(PWG_ERR_INVALID, where + "bad residual buffer");
     }
     if (op.out_div == 0.f) { delete n; return fail(PWG_ERR_INVALID, where + "out_div must be non-zero"); }
+    if (sconv) {
+      // Conv1d(kernel 2 stride, stride, padding) from a buffer of `stride` times the destination's rate
+      const PwgCnetSrc& src = op.src[0];
+      const char* bad = nullptr;
+      if (op.stride < 2 || op.stride > 8) bad = "strided conv: stride must be 2..8";
+      else if (src.taps != 2 * op.stride) bad = "strided conv: taps must be 2 * stride";
+      else if (rate[src.buf] != op.stride * rate[op.dst]) bad = "strided conv: source rate must be stride * destination rate";
+      else if (op.padding < 0 || op.padding >= 2 * op.stride) bad = "strided conv: padding must be within the kernel";
+      else if (src.dilation != 1 || src.pad_mode != PWG_PAD_ZERO || src.normalize) bad = "strided conv: dilation 1, zero padding, no normalize";
+      else if (src.channels % 16 != 0) bad = "strided conv: source channels must be a multiple of 16";
+      else if (op.src[1].buf >= 0 || op.res >= 0 || op.accumulate || op.out_div != 1.f || op.b2_off >= 0)
+        bad = "strided conv: one source, no residual / accumulate / division / second bias";
+      else if (op.dst == n_bufs - 1) bad = "strided conv: cannot write the program output";
+      if (bad) { delete n; return fail(PWG_ERR_UNSUPPORTED, where + bad); }
+    }
     const int mt_total0 = (op.out_channels + 31) / 32;
     int MT = pick_mt(mt_total0);
     // >= 256-row single-source convs with <= 7 taps run 2 m-tiles per x-tile workgroup (half the A
@@ -3905,7 +3934,7 @@ int pwg_cnet_create(const PwgCnetOp* ops, int n_ops, int n_bufs, const int* chan
       const int s = op.stride;
       // causal (CausalConvTranspose1d): replicate-padded source, no padding, T -> stride*T after the trim
       const bool causal = op.src[0].pad_mode == PWG_PAD_REPLICATE;
-      if (s < 1 || rate[op.dst] != s * rate[op.src[0].buf] ||
+      if (s < 1 || rate[op.dst] != s * rate[op.src[0].buf] || (nsrc == 2 && rate[op.src[1].buf] != rate[op.src[0].buf]) ||
           (causal ? op.padding != 0 || op.output_padding != 0 : s - 2 * op.padding + op.output_padding != 0)) {
         delete n;
         return fail(PWG_ERR_UNSUPPORTED, where + "ConvTranspose1d must map T -> stride*T (kernel 2*stride)");
@@ -3914,7 +3943,13 @@ int pwg_cnet_create(const PwgCnetOp* ops, int n_ops, int n_bufs, const int* chan
         delete n;
         return fail(PWG_ERR_UNSUPPORTED, where + "reflection padding on a ConvTranspose1d");
       }
-      if (!check_w(op.src[0].w_off, (long long)op.src[0].channels * op.out_channels * 2 * s)) {
+      // two sources (the channel concatenation [src[0]; src[1]] of one weight tensor at src[0].w_off)
+      if (nsrc == 2 && (causal || op.src[1].pad_mode != PWG_PAD_ZERO || op.src[0].normalize || op.src[1].normalize)) {
+        delete n;
+        return fail(PWG_ERR_UNSUPPORTED, where + "a two-source ConvTranspose1d is zero-padded and not normalized");
+      }
+      if (!check_w(op.src[0].w_off, (long long)(op.src[0].channels + (nsrc == 2 ? op.src[1].channels : 0)) *
+                                        op.out_channels * 2 * s)) {
         delete n;
         return fail(PWG_ERR_INVALID, where + "weights out of range");
       }
@@ -3968,9 +4003,18 @@ int pwg_cnet_create(const PwgCnetOp* ops, int n_ops, int n_bufs, const int* chan
       if (op.kind == PWG_CNET_CONVT) {
         ph.k_a = (r + op.padding) % op.stride;
         ph.off_a = (r + op.padding) / op.stride;
-        const int cs = (op.src[0].channels + CN_CHUNK - 1) / CN_CHUNK;
-        for (int k = 0; k < 2; ++k)
-          for (int c = 0; c < cs; ++c) ph.chunks.push_back({0, ph.off_a - k, c * CN_CHUNK, 0});
+        for (int s2 = 0; s2 < nsrc; ++s2) {
+          const int cs = (op.src[s2].channels + CN_CHUNK - 1) / CN_CHUNK;
+          for (int k = 0; k < 2; ++k)
+            for (int c = 0; c < cs; ++c) ph.chunks.push_back({s2, ph.off_a - k, c * CN_CHUNK, 0});
+        }
+      } else if (sconv) {
+        // channel-block-major: pwg_uconv.hip stages a 16-channel block once for all 2 stride taps
+        ph.sconv = true;
+        ph.k_a = ph.off_a = 0;
+        const int cs = op.src[0].channels / CN_CHUNK;
+        for (int c = 0; c < cs; ++c)
+          for (int k = 0; k < op.src[0].taps; ++k) ph.chunks.push_back({0, -op.padding + k, c * CN_CHUNK, 0});
       } else {
         ph.k_a = ph.off_a = 0;
         for (int s = 0; s < nsrc; ++s) {
@@ -4385,6 +4429,7 @@ int pwg_cnet_pack_weights(const PwgCnet* n, const float* ref, float* packed) {
       const ChunkDesc& cd = ph.chunks[c];
       const PwgCnetSrc& src = op.src[cd.src];
       const int tap = op.kind == PWG_CNET_CONVT ? ph.off_a - cd.row_off   // 0 or 1
+                      : ph.sconv                ? cd.row_off + op.padding
                                                 : (cd.row_off + src.pad) / src.dilation;
       for (int m = 0; m < ph.mt_total; ++m)
         for (int sub = 0; sub < 2; ++sub)
@@ -4437,6 +4482,7 @@ int pwg_cnet_plan_create(PwgCnet* n, int n_utts, const long long* frames, PwgCne
   const int nb = (int)n->channels.size();
   PwgCnetPlan* p = new PwgCnetPlan();
   p->n = n;
+  n->planned = true;
   p->n_utts = n_utts;
   p->pair_steps = n->pair_steps;
   p->frames.assign(frames, frames + n_utts);
@@ -4483,7 +4529,8 @@ int pwg_cnet_plan_create(PwgCnet* n, int n_utts, const long long* frames, PwgCne
     size_t o = 0;
     p->buf_off.assign(nb, SIZE_MAX);
     std::vector<int> order;
-    for (int b = 1; b < nb - 1; ++b) order.push_back(b);
+    for (int b = 1; b < nb - 1; ++b)
+      if (b != n->ext_buf) order.push_back(b);  // (the external buffer is the caller's: no slot)
     std::sort(order.begin(), order.end(), [&](int x, int y) { return first_def[x] < first_def[y]; });
     for (int b : order) {
       const size_t bytes = ((size_t)p->rows[b] * n->ld[b] * sizeof(float) + 255) / 256 * 256;
@@ -4579,7 +4626,7 @@ int pwg_cnet_plan_create(PwgCnet* n, int n_utts, const long long* frames, PwgCne
     if (!pq && ph.NW != 4 && ph.NW != 8) return bad_list(pi, "waves per workgroup");
     const int os = pq ? 1 : ph.ostride, oph = pq ? 0 : ph.ophase;
     for (int u = 0; u < n_utts; ++u) ncols[u] = (int)cn_list_cols(CN_L_NCOL, frames[u], rate, os, oph);
-    const int blk_step = pq ? 256 : (ph.thin ? CN_COLS : 32 * ph.NW);
+    const int blk_step = pq ? 256 : (ph.sconv ? SCONV_COLS : (ph.thin ? CN_COLS : 32 * ph.NW));
     const long long n_blk = count(blk_step);
     if (n_blk > (long long)INT32_MAX / 2) return bad_list(pi, "block count");
     p->o_blocks.push_back(list(CN_L_BLK, rate, os, oph, blk_step));
@@ -4611,7 +4658,8 @@ int pwg_cnet_plan_create(PwgCnet* n, int n_utts, const long long* frames, PwgCne
     // 1x1s; not the fused tap-major pairs / stacks): 1-2 waves, 1-2 m-tiles, CN_NARROW_G chunks per
     // barrier
     const bool tap_family = !xt_family && !ph.thin && !pq && ph.z_phases > 0 && ph.pair_b < 0 &&
-                            !(pi > 0 && n->phases[pi - 1].pair_b == (int)pi) && ph.stack_b < 0 && !ph.xt_convt_db;
+                            !(pi > 0 && n->phases[pi - 1].pair_b == (int)pi) && ph.stack_b < 0 && !ph.xt_convt_db &&
+                            !ph.sconv && !(convt && op.src[1].buf >= 0);  // (those two: their default launches)
     const long long zn = ph.z_phases;
     int pick_w = 0, pick_m = 1;
     if (n->narrow && xt_family && (convt || (op.src[0].taps - 1) * op.src[0].dilation <= NARROW_HALO)) {
@@ -4885,19 +4933,37 @@ long long pwg_cnet_plan_rows(const PwgCnetPlan* p, int buf) {
 
 long long pwg_cnet_plan_workspace_bytes(const PwgCnetPlan* p) { return p ? (long long)p->ws_bytes : -1; }
 
-int pwg_cnet_run(PwgCnetPlan* p, const float* packed, const float* mel, const float* mean, const float* scale,
-                 float* out, void* workspace, void* stream) {
+int pwg_cnet_plan_buffer(const PwgCnetPlan* p, int buf, long long* offset_bytes, long long* rows, int* ld) {
+  if (!p || !offset_bytes || !rows || !ld) return fail(PWG_ERR_INVALID, "null argument");
+  const int nb = (int)p->rows.size();
+  if (buf < 1 || buf >= nb - 1 || buf == p->n->ext_buf)
+    return fail(PWG_ERR_INVALID, "not a workspace buffer (the input, the output and the external buffer are the caller's)");
+  *offset_bytes = (long long)p->buf_off[buf];
+  *rows = p->rows[buf];
+  *ld = p->n->ld[buf];
+  return PWG_OK;
+}
+
+}  // extern "C"
+
+// pwg_cnet_run / pwg_cnet_run_ext: `ext` is the external buffer's rows (null without one)
+static int cnet_run(PwgCnetPlan* p, const float* packed, const float* mel, const float* mean, const float* scale,
+                    const float* ext, float* out, void* workspace, void* stream) {
   if (!p || !packed || !mel || !out || !workspace) return fail(PWG_ERR_INVALID, "null argument");
   if (p->host_only) return fail(PWG_ERR_INVALID, "a plan of a host-only handle (device -1) cannot run");
   PwgCnet* n = p->n;
   const int nb = (int)n->channels.size();
+  if (n->ext_buf >= 0 && !ext)
+    return fail(PWG_ERR_INVALID, "the program has an external buffer: run it with pwg_cnet_run_ext");
+  if (n->ext_buf < 0 && ext) return fail(PWG_ERR_INVALID, "the program has no external buffer (pwg_cnet_set_external)");
   Guard g(n->device);
   if (!g.ok) return fail(PWG_ERR_HIP, "hipSetDevice failed");
   hipStream_t const s_main = (hipStream_t)stream;
   std::vector<float*> bufs(nb);
   bufs[0] = const_cast<float*>(mel);
   bufs[nb - 1] = out;
-  for (int b = 1; b < nb - 1; ++b) bufs[b] = (float*)((char*)workspace + p->buf_off[b]);
+  for (int b = 1; b < nb - 1; ++b)
+    bufs[b] = b == n->ext_buf ? const_cast<float*>(ext) : (float*)((char*)workspace + p->buf_off[b]);
   int* const img = (int*)((char*)workspace + p->ws_img);
   auto i2 = [&](int off) -> const int2* { return off < 0 ? nullptr : reinterpret_cast<const int2*>(img + off); };
   auto i1 = [&](int off) -> const int* { return off < 0 ? nullptr : img + off; };
@@ -5179,13 +5245,24 @@ int pwg_cnet_run(PwgCnetPlan* p, const float* packed, const float* mel, const fl
       a.range_flag = op.dst == nb - 1 ? rflag : nullptr;
       out_checked |= op.dst == nb - 1;
       hipLaunchKernelGGL(pwg_cnet_pqmf_kernel, dim3((unsigned)p->n_blocks[pi]), dim3(256), 0, s, a);
+    } else if (op.kind == PWG_CNET_SCONV) {
+      SconvArgs a;
+      const PwgCnetSrc& src = op.src[0];
+      a.x = bufs[src.buf]; a.seg_x = seg_of(src.buf); a.ld_x = n->ld[src.buf]; a.slope = src.pre_slope;
+      a.w = packed + (n->split_f16 ? ph.frag16_off : ph.frag_off); a.bias = packed + ph.bias_off;
+      a.y = bufs[op.dst]; a.seg_y = seg_of(op.dst); a.ld_y = n->ld[op.dst]; a.M = op.out_channels;
+      a.mt_total = ph.mt_total; a.post_act = op.post_act; a.post_slope = op.post_slope;
+      a.blocks = i2(p->o_blocks[pi]); a.n_blocks = p->n_blocks[pi];
+      a.stride = op.stride; a.padding = op.padding; a.cs = src.channels / CN_CHUNK;
+      const hipError_t ea2 = launch_sconv(a, n->split_f16 != 0, s);
+      if (ea2 != hipSuccess) return hipf(ea2, "strided conv launch");
     } else if (p->n_blocks[pi] > 0) {
       CnConvArgs a;
       a.range_flag = nullptr;
       a.xcd_order = n->xcd_order;
       a.n_oimg = 0;
       a.oimg_rowb = n->channels[op.dst] * 4;
-      const int nsrc = (op.src[1].buf >= 0 && op.kind == PWG_CNET_CONV) ? 2 : 1;
+      const int nsrc = op.src[1].buf >= 0 ? 2 : 1;  // (CONV and CONVT; SCONV and PQMF ran above)
       for (int si = 0; si < 2; ++si) {
         const PwgCnetSrc& src = op.src[si];
         CnSrc& d = a.src[si];
@@ -5468,6 +5545,32 @@ int pwg_cnet_run(PwgCnetPlan* p, const float* packed, const float* mel, const fl
     n->records.push_back({-1, run_a, run_b});
     run_a = nullptr;  // (recorded: no longer the guard's)
   }
+  return PWG_OK;
+}
+
+extern "C" {
+
+int pwg_cnet_run(PwgCnetPlan* p, const float* packed, const float* mel, const float* mean, const float* scale,
+                 float* out, void* workspace, void* stream) {
+  return cnet_run(p, packed, mel, mean, scale, nullptr, out, workspace, stream);
+}
+
+int pwg_cnet_run_ext(PwgCnetPlan* p, const float* packed, const float* mel, const float* mean, const float* scale,
+                     const float* ext, float* out, void* workspace, void* stream) {
+  if (!ext) return fail(PWG_ERR_INVALID, "null argument");
+  return cnet_run(p, packed, mel, mean, scale, ext, out, workspace, stream);
+}
+
+int pwg_cnet_set_external(PwgCnet* n, int buf) {
+  if (!n) return fail(PWG_ERR_INVALID, "null argument");
+  const int nb = (int)n->channels.size();
+  if (n->planned) return fail(PWG_ERR_INVALID, "pwg_cnet_set_external must be called before the first plan");
+  if (n->ext_buf >= 0) return fail(PWG_ERR_UNSUPPORTED, "one external buffer besides buffer 0");
+  if (buf < 1 || buf >= nb - 1) return fail(PWG_ERR_INVALID, "the external buffer must be an internal buffer (1 .. n_bufs - 2)");
+  for (const PwgCnetOp& op : n->ops)
+    if (op.dst == buf) return fail(PWG_ERR_INVALID, "the external buffer must have no writer");
+  if (n->channels[buf] % 16) return fail(PWG_ERR_UNSUPPORTED, "external buffer channels must be a multiple of 16");
+  n->ext_buf = buf;
   return PWG_OK;
 }
 

@@ -394,6 +394,30 @@ int rstack_lds(int cs);
 // resident: the weight-resident form where the fragments fit the LDS (<= 64 channels), else streamed
 hipError_t launch_rstack(const RstackArgs& a, int cs, int n_wg, hipStream_t s, bool resident = true);
 
+// Strided conv of the conv-network executor (PWG_CNET_SCONV, pwg_uconv.hip): Conv1d(kernel 2 stride,
+// stride, padding) over the executor's time-major buffers, y[q] = post(b + sum W x[q stride - padding + k]).
+// One workgroup: SCONV_COLS output columns of one utterance x up to 4 m-tiles (128 output rows).
+constexpr int SCONV_COLS = 64;
+struct SconvArgs {
+  const float* x;        // source [rows][ld_x]
+  const int* seg_x;      // [n_utts][2] (first row, rows)
+  int ld_x;
+  float slope;           // LeakyReLU on load (1 = identity)
+  const float* w;        // A fragments [channel block][tap][mt_total][2][64][4], fp32 or fp16-pair image
+  const float* bias;     // mt_total * 32 floats
+  float* y;              // destination [rows][ld_y], ld_y a multiple of 4
+  const int* seg_y;
+  int ld_y, M, mt_total;
+  int post_act;          // PWG_ACT_*
+  float post_slope;
+  const int2* blocks;    // (utterance, first column), step SCONV_COLS
+  int n_blocks;
+  int stride, padding;
+  int cs;                // 16-channel blocks of the source
+};
+int sconv_lds(int stride);
+hipError_t launch_sconv(const SconvArgs& a, bool split, hipStream_t s);
+
 // Run status bits (the per-run word pwg_run_status reads, and the handle's sticky copy).
 constexpr int PWG_STATUS_RANGE = 1;         // a value left the fp16 pair range: rerun in exact fp32
 constexpr int PWG_STATUS_PIPE_TIMEOUT = 2;  // layer pipeline: a dependency wait gave up

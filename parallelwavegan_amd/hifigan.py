@@ -69,6 +69,38 @@ def _conv_bias(seq, key):
     return key + ".1.bias" if conv.bias is not None else None
 
 
+def lower_mrf(P, blocks, first, num_blocks, prefix, x_in, ch, rate):
+    """One multi-receptive-field stage (models/hifigan.py:186-190, models/uhifigan.py:276-281,
+    293-297): the average of ``num_blocks`` parallel HiFiGANResidualBlocks ``blocks[first + j]``
+    (state-dict keys ``{prefix}.{first + j}``) over the ``ch``-channel buffer ``x_in``. Returns the
+    buffer holding the average. Shared by lower_hifigan and the UHiFiGAN lowering (uhifigan.py)."""
+    acc = P.buffer(ch, rate)
+    for j in range(num_blocks):
+        blk = blocks[first + j]
+        bkey = f"{prefix}.{first + j}"
+        x = x_in
+        nd = len(blk.convs1)
+        for d in range(nd):
+            last = d == nd - 1
+            c1 = blk.convs1[d]
+            k1 = f"{bkey}.convs1.{d}"
+            fin = dict(accumulate=j > 0, out_div=float(num_blocks) if j == num_blocks - 1 else 1.0)
+            if blk.use_additional_convs:
+                t = P.buffer(ch, rate)
+                P.conv(k1, t, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1))
+                c2 = blk.convs2[d]
+                k2 = f"{bkey}.convs2.{d}"
+                dst = acc if last else P.buffer(ch, rate)
+                P.conv(k2, dst, ch, [_conv_src(P, t, ch, c2, k2)], bias=_conv_bias(c2, k2), res=x,
+                       **(fin if last else {}))
+            else:
+                dst = acc if last else P.buffer(ch, rate)
+                P.conv(k1, dst, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1), res=x,
+                       **(fin if last else {}))
+            x = dst
+    return acc
+
+
 def lower_hifigan(m):
     """The conv-network program of a HiFiGAN body (models/hifigan.py:173-192): ``m`` holds
     input_conv, upsamples, blocks and output_conv with the layout of HiFiGANGenerator. Buffer 0 is
@@ -104,30 +136,7 @@ def lower_hifigan(m):
         P.convt(key, up, ct.out_channels, src, s, padding, output_padding,
                 bias=key + ".bias" if ct.bias is not None else None)
         ch = ct.out_channels
-        acc = P.buffer(ch, rate)
-        for j in range(m.num_blocks):
-            blk = m.blocks[i * m.num_blocks + j]
-            bkey = f"blocks.{i * m.num_blocks + j}"
-            x = up
-            nd = len(blk.convs1)
-            for d in range(nd):
-                last = d == nd - 1
-                c1 = blk.convs1[d]
-                k1 = f"{bkey}.convs1.{d}"
-                fin = dict(accumulate=j > 0, out_div=float(m.num_blocks) if j == m.num_blocks - 1 else 1.0)
-                if blk.use_additional_convs:
-                    t = P.buffer(ch, rate)
-                    P.conv(k1, t, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1))
-                    c2 = blk.convs2[d]
-                    k2 = f"{bkey}.convs2.{d}"
-                    dst = acc if last else P.buffer(ch, rate)
-                    P.conv(k2, dst, ch, [_conv_src(P, t, ch, c2, k2)], bias=_conv_bias(c2, k2), res=x,
-                           **(fin if last else {}))
-                else:
-                    dst = acc if last else P.buffer(ch, rate)
-                    P.conv(k1, dst, ch, [_conv_src(P, x, ch, c1, k1)], bias=_conv_bias(c1, k1), res=x,
-                           **(fin if last else {}))
-                x = dst
+        acc = lower_mrf(P, m.blocks, i * m.num_blocks, m.num_blocks, "blocks", up, ch, rate)
         cur = acc
     out = P.buffer(m.out_channels, rate)
     P.conv("output_conv.1", out, m.out_channels, [_conv_src(P, cur, ch, m.output_conv, "output_conv")],

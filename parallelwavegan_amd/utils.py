@@ -19,7 +19,7 @@ import torch
 import yaml
 
 GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator", "DiscreteSymbolHiFiGANGenerator",
-              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator")
+              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator", "UHiFiGANGenerator")
 
 
 def generator_class(name):
@@ -28,12 +28,13 @@ def generator_class(name):
     from .hifigan import HiFiGANGenerator
     from .melgan import MelGANGenerator
     from .models import ParallelWaveGANGenerator
+    from .uhifigan import UHiFiGANGenerator
 
     table = {"ParallelWaveGANGenerator": ParallelWaveGANGenerator, "MelGANGenerator": MelGANGenerator,
              "HiFiGANGenerator": HiFiGANGenerator,
              "DiscreteSymbolHiFiGANGenerator": DiscreteSymbolHiFiGANGenerator,
              "DiscreteSymbolDurationGenerator": DiscreteSymbolDurationGenerator,
-             "DiscreteSymbolF0Generator": DiscreteSymbolF0Generator}
+             "DiscreteSymbolF0Generator": DiscreteSymbolF0Generator, "UHiFiGANGenerator": UHiFiGANGenerator}
     if name not in table:
         raise NotImplementedError(f"generator_type {name!r} is not accelerated (supported: {', '.join(GENERATORS)})")
     return table[name]
