@@ -12,6 +12,8 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
   StyleMelGANGenerator      drop-in StyleMelGAN generator on the TADE kernels (include/pwg_smg.h)
   UHiFiGANGenerator         drop-in U-Net HiFiGAN (mel + excitation): HIP excitation front end, strided
                             and two-source transposed convs on the conv-network executor
+  VQVAE                     drop-in VQ-VAE (waveform -> codes -> waveform): HIP grouped strided encoder
+                            levels, nearest-code search and decoder front end (include/pwg_vq.h)
 """
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
@@ -20,5 +22,6 @@ from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Gene
 from .models import ParallelWaveGANGenerator  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401
 from .uhifigan import UHiFiGANGenerator  # noqa: F401
+from .vqvae import VQVAE  # noqa: F401
 
 __version__ = "0.1.0"

@@ -31,6 +31,7 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_embed_ext.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_smg.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_uconv.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_vq.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
@@ -38,6 +39,7 @@ HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg_embed.h"),
     os.path.join(REPO_DIR, "include", "pwg_smg.h"),
     os.path.join(REPO_DIR, "include", "pwg_uhg.h"),
+    os.path.join(REPO_DIR, "include", "pwg_vq.h"),
     os.path.join(PKG_DIR, "csrc", "pwg_internal.h"),
 ]
 OFFLOAD_ARCH = "gfx950"
@@ -122,6 +124,15 @@ EXPORTED_SYMBOLS = (
     "pwg_embed_rows_f0",
     # include/pwg_uhg.h: UHiFiGAN's excitation front end (csrc/pwg_uconv.hip)
     "pwg_uhg_excite_rows",
+    # include/pwg_vq.h: VQVAE's encoder front end, grouped strided levels, code search and decoder rows
+    # (csrc/pwg_vq.hip)
+    "pwg_vq_wave_rows",
+    "pwg_vq_gsconv_packed_count",
+    "pwg_vq_gsconv_pack",
+    "pwg_vq_gsconv",
+    "pwg_vq_code_norms",
+    "pwg_vq_nearest",
+    "pwg_vq_decode_rows",
     # include/pwg_smg.h: StyleMelGAN generator path
     "pwg_smg_create",
     "pwg_smg_destroy",
@@ -151,6 +162,8 @@ PWG_OPT_SYNC_ABORT = 7
 PWG_OPT_SYNC_TIMEOUT = 8
 PWG_OPT_FRAGMENT_AHEAD = 9
 
+
+PWG_VQ_BAD_CODE, PWG_VQ_BAD_GLOBAL, PWG_VQ_BAD_INPUT = 1, 2, 4
 
 PWG_SMG_MAX_SCALES = 16
 PWG_SMG_STATS_TILE = 128
@@ -395,6 +408,15 @@ def load():
         lib.pwg_regulate_rows.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci, ll, ll, vp, vp, vp]
         lib.pwg_embed_rows_f0.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ll, vp, vp, vp]
         lib.pwg_uhg_excite_rows.argtypes = [vp, vp, vp, ci, ci, ctypes.c_float, vp, ci, ll, vp, vp]
+        cf = ctypes.c_float
+        lib.pwg_vq_wave_rows.argtypes = [vp, vp, vp, ci, ci, cf, vp, vp, ci, ll, vp, vp]
+        lib.pwg_vq_gsconv_packed_count.argtypes = [ci, ci, ci]
+        lib.pwg_vq_gsconv_packed_count.restype = ll
+        lib.pwg_vq_gsconv_pack.argtypes = [vp, ci, ci, ci, vp]
+        lib.pwg_vq_gsconv.argtypes = [vp, vp, ll, ci, vp, vp, ci, ci, cf, vp, vp, ll, ci, vp]
+        lib.pwg_vq_code_norms.argtypes = [vp, ci, ci, vp, vp]
+        lib.pwg_vq_nearest.argtypes = [vp, ll, ci, vp, vp, ci, vp, vp, vp, vp]
+        lib.pwg_vq_decode_rows.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, ci, vp, ci, ci, vp, vp, ci, ll, vp, vp, vp]
         lib.pwg_smg_create.argtypes = [ctypes.POINTER(PwgSmgConfig), ctypes.c_int, ctypes.POINTER(vp)]
         lib.pwg_smg_destroy.argtypes = [vp]
         lib.pwg_smg_destroy.restype = None

@@ -20,7 +20,12 @@ Same arguments for the mel-to-wave case (--dumpdir with ``*-feats.npy`` files, -
     durations: no further device-to-host traffic);
   * UHiFiGANGenerator reads ``*-excitation.npy`` beside each ``*-feats.npy`` (bin/decode.py:188-192 of
     the reference) and fails before any decoding when one is missing; ``*-f0.npy`` is read if present
-    and otherwise ignored (the generator never uses f0, models/uhifigan.py:261-301).
+    and otherwise ignored (the generator never uses f0, models/uhifigan.py:261-301);
+  * VQVAE takes the reference's VQ-WAV2WAV branch (bin/decode.py:274-387) for ``format: npy`` dumps: it
+    reads ``*-wave.npy`` (and ``*-local.npy`` / ``*-global.npy`` beside each when the config sets
+    use_local_condition / use_global_condition), runs wav -> codes -> wav over ragged batches
+    (VQVAE.inference_batch), writes ``<utt>_gen.wav`` and ``<outdir>/text`` with ``utt_id sym sym ...``
+    per line. One process only.
 """
 
 import argparse
@@ -75,6 +80,75 @@ def excitation_files(feats_files):
     return paths
 
 
+def vq_condition_files(wave_files, use_local, use_global):
+    """The ``*-local.npy`` / ``*-global.npy`` files beside each ``*-wave.npy`` (None for a part the
+    config does not use); raises FileNotFoundError naming the first missing one."""
+    out = []
+    for on, tag in ((use_local, "local"), (use_global, "global")):
+        if not on:
+            out.append(None)
+            continue
+        paths = [f[:-len("-wave.npy")] + f"-{tag}.npy" for f in wave_files]
+        missing = [p for p in paths if not os.path.exists(p)]
+        if missing:
+            raise FileNotFoundError(f"use_{tag}_condition is set: VQVAE needs a {tag} dump beside every wave file: "
+                                    f"{len(missing)} missing, first {missing[0]}")
+        out.append(paths)
+    return out
+
+
+def decode_vq(args, config, model, device):
+    """The VQ-WAV2WAV branch: every ``*-wave.npy`` of --dumpdir through VQVAE.inference_batch."""
+    from parallelwavegan_amd.utils import find_files, log_rtf, write_pcm16_wav
+
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("VQVAE decoding is not sharded: run one process")
+    files = find_files(args.dumpdir, "*-wave.npy")
+    use_local, use_global = bool(config.get("use_local_condition")), bool(config.get("use_global_condition"))
+    local_files, global_files = vq_condition_files(files, use_local, use_global)
+    utt_ids = [os.path.basename(f).replace("-wave.npy", "") for f in files]
+    lengths = [int(np.prod(np.load(f, mmap_mode="r", allow_pickle=False).shape)) for f in files]
+    logging.info(f"The number of features to be decoded = {len(files)}.")
+    hop = model.downsample_factor
+    limit = args.batch_frames * hop if args.batch_frames is not None else 1 << 22  # samples per pass
+    sr = config["sampling_rate"]
+    model.remove_weight_norm()
+    model = model.eval().to(device)
+    batches, cur, n = [], [], 0
+    for i, t in enumerate(lengths):
+        if cur and n + t > limit:
+            batches.append(cur)
+            cur, n = [], 0
+        cur.append(i)
+        n += t
+    if cur:
+        batches.append(cur)
+    total_rtf, done = 0.0, 0
+    with open(os.path.join(config["outdir"], "text"), "w") as text:
+        for batch in batches:
+            xs = [np.ascontiguousarray(np.load(files[i], allow_pickle=False), np.float32).reshape(-1) for i in batch]
+            ls = gs = None
+            if use_local:
+                ls = [np.ascontiguousarray(np.load(local_files[i], allow_pickle=False), np.float32) for i in batch]
+            if use_global:
+                gs = [int(np.asarray(np.load(global_files[i], allow_pickle=False)).reshape(-1)[0]) for i in batch]
+            start = time.time()
+            with torch.no_grad():
+                ys, zs = model.inference_batch(xs, ls, gs)
+                ys = [y.view(-1).cpu().numpy() for y in ys]
+                zs = [z.view(-1).cpu().numpy() for z in zs]
+            el = time.time() - start
+            total_rtf += el / (sum(len(y) for y in ys) / sr) * len(ys)
+            done += len(ys)
+            for i, y, z in zip(batch, ys, zs):
+                write_pcm16_wav(os.path.join(config["outdir"], f"{utt_ids[i]}_gen.wav"), y, sr)
+                text.write(f"{utt_ids[i]} {' '.join(str(int(v)) for v in z)}\n")
+    log_rtf(done, total_rtf)
+    for eng in (model._tail, model.decoder.engine(False)):
+        eng.release_workspace()
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Decode dumped features with the MI355X generator engine.")
     ap.add_argument("--scp", default=None, type=str)
@@ -100,7 +174,8 @@ def main(argv=None):
     from parallelwavegan_amd.utils import find_files, load_model, log_rtf, read_config, write_pcm16_wav
 
     if args.scp is not None or args.segments is not None:
-        raise NotImplementedError("--scp/--segments need kaldiio, which is not available; use --dumpdir")
+        raise NotImplementedError("--scp/--segments need kaldiio, which is not available; use --dumpdir (for a VQVAE: "
+                                  "a --dumpdir of *-wave.npy files)")
     if args.dumpdir is None:
         raise ValueError("Please specify either --dumpdir or --feats-scp.")
     os.makedirs(args.outdir, exist_ok=True)
@@ -127,6 +202,10 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
 
     model = load_model(args.checkpoint, config)
+    if config.get("generator_type") == "VQVAE":
+        if args.use_f0 or args.normalize_before:
+            raise NotImplementedError("--use-f0 / --normalize-before do not apply to a VQVAE (it decodes waveforms)")
+        return decode_vq(args, config, model, device)
     if args.normalize_before:
         assert hasattr(model, "mean"), "Feature stats are not registered."
         assert hasattr(model, "scale"), "Feature stats are not registered."

@@ -268,3 +268,41 @@ def uhifigan_params(name, **overrides):
     p = copy.deepcopy(UHIFIGAN_PARAMS[name])
     p.update(copy.deepcopy(overrides))
     return p
+
+
+# VQVAE (models/vqvae.py:16-171), a table of its own: waveform in, codes and waveform out.
+#   vqvae_v3  egs/vctk/vq1/conf/local_conditioned_melgan_vae.v3.yaml (24 kHz, hop 64, local 2 -> 32,
+#             global 128 x 128, decoder in_channels 416); without the local part the decoder takes 384
+#             channels, without both 256 (overrides).
+# ``*_test`` are reduced shapes: ``a`` has a level of 16 outputs per group and one of 4 (the width
+# cap), 48 codes and both conditionings; ``b`` two levels of 8 outputs per group, 33 codes, no
+# conditioning and no encoder biases.
+VQVAE_PARAMS = {
+    "vqvae_v3": dict(in_channels=1, out_channels=1, num_embeds=512, embed_dim=256, num_local_embeds=2,
+                     local_embed_dim=32, num_global_embeds=128, global_embed_dim=128,
+                     encoder_type="MelGANDiscriminator", decoder_type="MelGANGenerator",
+                     encoder_conf=dict(out_channels=256, downsample_scales=[4, 4, 2, 2], max_downsample_channels=1024),
+                     decoder_conf=dict(in_channels=416, upsample_scales=[4, 4, 2, 2], channels=512, stacks=3),
+                     use_weight_norm=True),
+    "vqvae_test_a": dict(in_channels=1, out_channels=1, num_embeds=48, embed_dim=32, num_local_embeds=2,
+                         local_embed_dim=16, num_global_embeds=5, global_embed_dim=16,
+                         encoder_type="MelGANDiscriminator", decoder_type="MelGANGenerator",
+                         encoder_conf=dict(channels=16, downsample_scales=[4, 2], max_downsample_channels=64,
+                                           out_channels=32),
+                         decoder_conf=dict(in_channels=64, channels=64, upsample_scales=[4, 2], stacks=2),
+                         use_weight_norm=True),
+    "vqvae_test_b": dict(in_channels=1, out_channels=1, num_embeds=33, embed_dim=32,
+                         encoder_type="MelGANDiscriminator", decoder_type="MelGANGenerator",
+                         encoder_conf=dict(channels=16, downsample_scales=[2, 2], max_downsample_channels=64,
+                                           out_channels=32, bias=False),
+                         decoder_conf=dict(in_channels=32, channels=64, upsample_scales=[2, 2], stacks=2),
+                         use_weight_norm=True),
+}
+SAMPLING_RATE.update(vqvae_v3=24000)
+
+
+def vqvae_params(name, **overrides):
+    """Deep-copied VQVAE constructor arguments of a recipe."""
+    p = copy.deepcopy(VQVAE_PARAMS[name])
+    p.update(copy.deepcopy(overrides))
+    return p

@@ -19,7 +19,7 @@ import torch
 import yaml
 
 GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator", "DiscreteSymbolHiFiGANGenerator",
-              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator", "UHiFiGANGenerator")
+              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator", "UHiFiGANGenerator", "VQVAE")
 
 
 def generator_class(name):
@@ -29,12 +29,14 @@ def generator_class(name):
     from .melgan import MelGANGenerator
     from .models import ParallelWaveGANGenerator
     from .uhifigan import UHiFiGANGenerator
+    from .vqvae import VQVAE
 
     table = {"ParallelWaveGANGenerator": ParallelWaveGANGenerator, "MelGANGenerator": MelGANGenerator,
              "HiFiGANGenerator": HiFiGANGenerator,
              "DiscreteSymbolHiFiGANGenerator": DiscreteSymbolHiFiGANGenerator,
              "DiscreteSymbolDurationGenerator": DiscreteSymbolDurationGenerator,
-             "DiscreteSymbolF0Generator": DiscreteSymbolF0Generator, "UHiFiGANGenerator": UHiFiGANGenerator}
+             "DiscreteSymbolF0Generator": DiscreteSymbolF0Generator, "UHiFiGANGenerator": UHiFiGANGenerator,
+             "VQVAE": VQVAE}
     if name not in table:
         raise NotImplementedError(f"generator_type {name!r} is not accelerated (supported: {', '.join(GENERATORS)})")
     return table[name]
@@ -71,7 +73,7 @@ def load_model(checkpoint, config=None, stats=None):
         cand = os.path.join(os.path.dirname(checkpoint), f"stats.{ext}")
         if os.path.exists(cand):
             stats = cand
-    if stats is not None:
+    if stats is not None and generator_type != "VQVAE":  # (utils/utils.py:343: a VQVAE takes no feature stats)
         model.register_stats(stats)
     if config["generator_params"].get("out_channels", 1) > 1:
         from .melgan import PQMF
