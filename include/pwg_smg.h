@@ -47,6 +47,19 @@ enum {
   PWG_SMG_KINDS = 7
 };
 
+/* pwg_smg_plan_create_ex flags */
+enum {
+  /* The layout of DiscreteSymbolStyleMelGANGenerator.inference (style_melgan.py:588-600): the upsampled
+   * noise is cut to the utterance's frames (x = noise_up[:, :, :T]) instead of the aux frames being
+   * padded up to it, so every tensor has exactly frames[u] rows per utterance at rate 1 and every
+   * instance-norm statistic is taken over them. */
+  PWG_SMG_PLAN_TRIM_NOISE = 1
+};
+
+/* Bits of the run's flag word (pwg_smg_run_status): a non-finite sample from the output kernel, and the
+ * PWG_EMBED_BAD_* bits of pwg_embed.h shifted left by PWG_SMG_FLAG_EMBED_SHIFT from the token staging. */
+enum { PWG_SMG_FLAG_NONFINITE = 1, PWG_SMG_FLAG_EMBED_SHIFT = 8 };
+
 typedef struct PwgSmgConfig {
   int in_channels;  /* noise channels */
   int aux_channels; /* multiple of 16, <= 128 */
@@ -88,6 +101,13 @@ PWG_API int pwg_smg_pack_weights(const PwgSmg* g, const float* ref_host, float* 
  * it, style_melgan.py:230-231). */
 PWG_API int pwg_smg_plan_create(const PwgSmg* g, int n_utts, const long long* frames, const long long* noise_len,
                                 PwgSmgPlan** out);
+/* flags = 0: exactly pwg_smg_plan_create. PWG_SMG_PLAN_TRIM_NOISE: utterance u owns frames[u] rows at
+ * rate 1 (row prefix(frames)[u] * rate of every tensor); frames[u] >= 2 is required (InstanceNorm1d over
+ * one row raises in the reference) and noise_len[u] * noise_factor >= frames[u] still holds: the last
+ * noise layer keeps its first frames[u] rows. Unknown flags are PWG_ERR_INVALID. pwg_smg_plan_tensor and
+ * pwg_smg_plan_out_rows report the trimmed layout. */
+PWG_API int pwg_smg_plan_create_ex(const PwgSmg* g, int n_utts, const long long* frames, const long long* noise_len,
+                                   int flags, PwgSmgPlan** out);
 PWG_API void pwg_smg_plan_destroy(PwgSmgPlan* p);
 PWG_API long long pwg_smg_plan_workspace_bytes(const PwgSmgPlan* p);
 /* output rows of the whole batch: sum of frames[u] * prod(upsample_scales) */
@@ -102,12 +122,29 @@ PWG_API long long pwg_smg_plan_out_rows(const PwgSmgPlan* p);
  * allocates nothing and does not synchronise (with timing off, below). */
 PWG_API int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const float* mean,
                         const float* scale, const float* z, float* out, void* workspace, void* stream);
+/* The token form (DiscreteSymbolStyleMelGANGenerator, style_melgan.py:364-602) on a plan made with
+ * PWG_SMG_PLAN_TRIM_NOISE: the aux input is c[r] = emb[ids[r]] + spk[spk_ids[u(r)]], gathered where the first
+ * aux conv stages its input (one fp32 add per element, as pwg_embed_rows; no (rows, aux_channels) buffer and
+ * no launch of its own). All device pointers. emb: num_embs x aux_channels, spk: num_spk x aux_channels,
+ * packed fp32, 16-byte aligned; ids: int64, the utterances' token ids back to back (sum frames); spk_ids:
+ * int64, one per utterance; the rest as pwg_smg_run. Every id is checked before an address is formed from
+ * it: a token id outside [0, num_embs) is staged as a zero row and sets PWG_EMBED_BAD_TOKEN <<
+ * PWG_SMG_FLAG_EMBED_SHIFT in the run's flag; a speaker id outside [0, num_spk) contributes zero and sets
+ * PWG_EMBED_BAD_SPEAKER << PWG_SMG_FLAG_EMBED_SHIFT. Launches only, as pwg_smg_run. The argument checks
+ * (PWG_ERR_INVALID: null pointers, alignment, a plan without PWG_SMG_PLAN_TRIM_NOISE, a host-only handle,
+ * another current device) come before any launch. */
+PWG_API int pwg_smg_run_tokens(const PwgSmgPlan* p, const float* packed, const float* emb, int num_embs,
+                               const float* spk, int num_spk, const long long* ids, const long long* spk_ids,
+                               const float* z, float* out, void* workspace, void* stream);
 /* Synchronises the stream and reads the run's flag: PWG_ERR_RANGE if a non-finite sample was stored
- * (a value left the fp16 pair range upstream, or the input was not finite). */
+ * (a value left the fp16 pair range upstream, or the input was not finite), or, after pwg_smg_run_tokens, if
+ * an id was out of range (the message starts with "bad token id" or "bad speaker id"; ids are reported
+ * first). */
 PWG_API int pwg_smg_run_status(const PwgSmgPlan* p, void* workspace, void* stream);
 
 /* Where a block's tensors lie in the workspace after pwg_smg_run (tests compare block by block).
- * rows counts the whole batch (utterance u starts at row prefix(noise_len * noise_factor)[u] * rate);
+ * rows counts the whole batch (utterance u starts at row prefix(noise_len * noise_factor)[u] * rate, or
+ * prefix(frames)[u] * rate in a trimmed plan);
  * for the statistics tables rows = n_utts and ld = 2 * channels. */
 PWG_API int pwg_smg_plan_tensor(const PwgSmgPlan* p, int block, int which, long long* offset_bytes,
                                 long long* rows, int* ld);

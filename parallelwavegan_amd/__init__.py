@@ -10,6 +10,9 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
                             its duration- and f0-conditioned siblings (HIP duration predictor, length
                             regulator and f0 / weighted-sum front ends)
   StyleMelGANGenerator      drop-in StyleMelGAN generator on the TADE kernels (include/pwg_smg.h)
+  DiscreteSymbolStyleMelGANGenerator
+                            its token form: ids and a speaker id gathered in the first aux conv's staging, the
+                            noise trimmed to the frames (pwg_smg_plan_create_ex, pwg_smg_run_tokens)
   UHiFiGANGenerator         drop-in U-Net HiFiGAN (mel + excitation): HIP excitation front end, strided
                             and two-source transposed convs on the conv-network executor
   VQVAE                     drop-in VQ-VAE (waveform -> codes -> waveform): HIP grouped strided encoder
@@ -18,6 +21,7 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
 from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
+from .dsym_stylemelgan import DiscreteSymbolStyleMelGANGenerator  # noqa: F401
 from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator  # noqa: F401
 from .models import ParallelWaveGANGenerator  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401

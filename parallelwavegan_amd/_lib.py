@@ -140,10 +140,12 @@ EXPORTED_SYMBOLS = (
     "pwg_smg_packed_weight_count",
     "pwg_smg_pack_weights",
     "pwg_smg_plan_create",
+    "pwg_smg_plan_create_ex",
     "pwg_smg_plan_destroy",
     "pwg_smg_plan_workspace_bytes",
     "pwg_smg_plan_out_rows",
     "pwg_smg_run",
+    "pwg_smg_run_tokens",
     "pwg_smg_run_status",
     "pwg_smg_plan_tensor",
     "pwg_smg_debug_stats",
@@ -169,6 +171,7 @@ PWG_SMG_MAX_SCALES = 16
 PWG_SMG_STATS_TILE = 128
 PWG_SMG_GATES = {"softmax": 0, "sigmoid": 1}
 PWG_SMG_X_IN, PWG_SMG_X_OUT, PWG_SMG_STATS_IN, PWG_SMG_STATS_MID = range(4)
+PWG_SMG_PLAN_TRIM_NOISE = 1
 PWG_SMG_KINDS = ("noise", "stats", "aux_conv", "modulate_conv", "gate_conv", "finalise", "output")
 
 
@@ -428,7 +431,10 @@ def load():
             getattr(lib, name).restype = ll
         lib.pwg_smg_pack_weights.argtypes = [vp, vp, vp]
         lib.pwg_smg_plan_create.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.POINTER(vp)]
+        lib.pwg_smg_plan_create_ex.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ll), ctypes.POINTER(ll), ctypes.c_int,
+                                               ctypes.POINTER(vp)]
         lib.pwg_smg_run.argtypes = [vp] * 9
+        lib.pwg_smg_run_tokens.argtypes = [vp, vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]
         lib.pwg_smg_run_status.argtypes = [vp, vp, vp]
         lib.pwg_smg_plan_tensor.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ll), ctypes.POINTER(ll),
                                             ctypes.POINTER(ctypes.c_int)]

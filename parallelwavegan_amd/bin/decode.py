@@ -25,7 +25,10 @@ Same arguments for the mel-to-wave case (--dumpdir with ``*-feats.npy`` files, -
     reads ``*-wave.npy`` (and ``*-local.npy`` / ``*-global.npy`` beside each when the config sets
     use_local_condition / use_global_condition), runs wav -> codes -> wav over ragged batches
     (VQVAE.inference_batch), writes ``<utt>_gen.wav`` and ``<outdir>/text`` with ``utt_id sym sym ...``
-    per line. One process only.
+    per line. One process only;
+  * DiscreteSymbolStyleMelGANGenerator reads (T, 2) [token id, speaker id] arrays from ``*-feats.npy`` like
+    every token vocoder; --spk-id (an addition) replaces the speaker column, so that (T,) or (T, 1) id files
+    decode too. It draws its noise on the device per batch.
 """
 
 import argparse
@@ -53,6 +56,17 @@ def batch_cost_model(model, device, frac=0.25, cap_gib=8.0, probe_frames=512, pr
     of ``probe_utts`` equal utterances of the same total length adds over the one-utterance probe
     (segment gaps and tile padding). Channel counts and samples per frame come from the model."""
     eng = model.engine()
+    if type(model).__name__ == "DiscreteSymbolStyleMelGANGenerator":
+        # a trimmed TADE plan; per frame besides it: two int64 ids, the noise column's share, the audio out
+        from parallelwavegan_amd._lib import PWG_SMG_PLAN_TRIM_NOISE as trim
+
+        nf, hop = int(model.noise_upsample_factor), int(model.upsample_factor)
+        each = probe_frames // probe_utts
+        one = eng.plan([probe_frames], [(probe_frames - 1) // nf + 1], trim).workspace_bytes
+        many = eng.plan([each] * probe_utts, [(each - 1) // nf + 1] * probe_utts, trim).workspace_bytes
+        per_frame = one / probe_frames + 16 + 4 * model.in_channels / nf + 4 * hop * model.out_channels
+        free, _ = torch.cuda.mem_get_info(device)
+        return per_frame, max(0.0, (many - one) / (probe_utts - 1)), min(free * frac, cap_gib * (1 << 30))
     if hasattr(model, "aux_channels"):  # ParallelWaveGANGenerator: mel in, noise in, audio out
         in_ch, hop, out_ch, noise = model.aux_channels, model.upsample_factor, model.out_channels, 1
     else:  # MelGAN family: the program's input channels, output rate (PQMF included) and channels
@@ -160,6 +174,9 @@ def main(argv=None):
     ap.add_argument("--normalize-before", default=False, action="store_true")
     ap.add_argument("--verbose", type=int, default=1)
     ap.add_argument("--use-f0", default=False, action="store_true")
+    ap.add_argument("--spk-id", type=int, default=None,
+                    help="DiscreteSymbolStyleMelGANGenerator only: the speaker id of every utterance (replaces the "
+                         "second column of the id files, which may then be (T,) or (T, 1))")
     ap.add_argument("--batch-frames", type=int, default=None,
                     help="max mel frames per engine pass (ragged batch); default: sized from free device "
                          "memory (--batch-mem-frac of it, at most --batch-mem-gib)")
@@ -217,6 +234,9 @@ def main(argv=None):
     if isinstance(model, DiscreteSymbolF0Generator) and model.use_f0 and not args.use_f0:
         raise ValueError("this generator was trained with use_f0: pass --use-f0 (and dump *-f0.npy files)")
     with_durations = isinstance(model, DiscreteSymbolDurationGenerator)
+    smg_tokens = type(model).__name__ == "DiscreteSymbolStyleMelGANGenerator"
+    if args.spk_id is not None and not smg_tokens:
+        raise NotImplementedError(f"--spk-id applies to a DiscreteSymbolStyleMelGANGenerator (got {type(model).__name__})")
     model.remove_weight_norm()
     model = model.eval().to(device)
 
@@ -280,6 +300,8 @@ def main(argv=None):
                                  for _, i in batch]
             if with_durations:
                 kwargs["ds"] = [durations[i] for _, i in batch]
+            if smg_tokens and args.spk_id is not None:
+                kwargs["g"] = args.spk_id
             if uhifigan:
                 excs = [np.ascontiguousarray(np.load(exc_files[i], allow_pickle=False), np.float32).reshape(-1)
                         for _, i in batch]

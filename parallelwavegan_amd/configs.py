@@ -235,6 +235,43 @@ def style_melgan_params(name, **overrides):
     return p
 
 
+# Token StyleMelGAN generators (DiscreteSymbolStyleMelGANGenerator, models/style_melgan.py:364-602;
+# dsym_stylemelgan.py): ids and a speaker id in, the TADE kernels with the token staging and the
+# trimmed layout (include/pwg_smg.h).
+#   dsym_style_melgan_hubert_v1  egs/vctk/hubert_voc1/conf/style_melgan_hubert.v1.yaml:25-45 (16 kHz, hop 320:
+#                                an odd noise scale, a factor-5 block and two factor-1 blocks)
+# ``*_test`` are reduced shapes: the softmax gate at aux 128, and a sigmoid gate with odd scales, with and
+# without biases.
+DSYM_STYLE_MELGAN_PARAMS = {
+    "dsym_style_melgan_hubert_v1": dict(in_channels=128, aux_channels=128, channels=64, out_channels=1, num_embs=100,
+                                        num_spk_embs=128, spk_emb_dim=128, concat_spk_emb=False, kernel_size=9,
+                                        dilation=2, bias=True, noise_upsample_scales=[7, 2, 2, 2],
+                                        noise_upsample_activation="LeakyReLU",
+                                        noise_upsample_activation_params={"negative_slope": 0.2},
+                                        upsample_scales=[5, 2, 2, 2, 2, 2, 2, 1, 1], upsample_mode="nearest",
+                                        gated_function="softmax", use_weight_norm=True),
+    "dsym_smg_test": dict(in_channels=32, aux_channels=128, channels=64, out_channels=1, num_embs=11, num_spk_embs=3,
+                          spk_emb_dim=128, concat_spk_emb=False, kernel_size=9, dilation=2, bias=True,
+                          noise_upsample_scales=[4, 2], noise_upsample_activation="LeakyReLU",
+                          noise_upsample_activation_params={"negative_slope": 0.2}, upsample_scales=[2, 2, 2, 1],
+                          upsample_mode="nearest", gated_function="softmax", use_weight_norm=True),
+    "dsym_smg_odd_test": dict(in_channels=32, aux_channels=32, channels=32, out_channels=1, num_embs=11,
+                              num_spk_embs=3, spk_emb_dim=32, concat_spk_emb=False, kernel_size=5, dilation=2,
+                              bias=True, noise_upsample_scales=[3, 2], noise_upsample_activation="LeakyReLU",
+                              noise_upsample_activation_params={"negative_slope": 0.2}, upsample_scales=[3, 1, 2],
+                              upsample_mode="nearest", gated_function="sigmoid", use_weight_norm=True),
+}
+DSYM_STYLE_MELGAN_PARAMS["dsym_smg_odd_nobias_test"] = dict(DSYM_STYLE_MELGAN_PARAMS["dsym_smg_odd_test"], bias=False)
+SAMPLING_RATE.update(dsym_style_melgan_hubert_v1=16000)
+
+
+def dsym_style_melgan_params(name, **overrides):
+    """Deep-copied DiscreteSymbolStyleMelGANGenerator constructor arguments of a recipe."""
+    p = copy.deepcopy(DSYM_STYLE_MELGAN_PARAMS[name])
+    p.update(copy.deepcopy(overrides))
+    return p
+
+
 # UHiFiGAN generators (models/uhifigan.py:19-387), a table of their own: they take an excitation
 # signal besides the mel, and the MelGAN-family tests iterate VOCODER_PARAMS.
 #   uhifigan_v1  egs/{opencpop,opensinger}/voc1/conf/uhifigan.v1.yaml (24 kHz singing, hop 300)

@@ -6,6 +6,9 @@
 // upsampled row) starts at row p0[u] * r, where p0 is the prefix sum of n0 = noise_len * noise_factor.
 // Every kernel takes a 2-D grid (tile or element block, utterance): a tile never spans two utterances,
 // and blocks past an utterance's end leave at once.
+// In a trimmed plan (PWG_SMG_PLAN_TRIM_NOISE, the token class of style_melgan.py:364-602) n0 = frames
+// instead: the last noise layer keeps rows t < frames only and everything after it has exactly
+// `frames` rows per utterance at rate 1.
 //
 // smg_conv_kernel<MT, NT, EPI>: a K-tap "same" conv as an MFMA GEMM, out[o][t] = sum_{tap, ci}
 // W[o][ci][tap] * in[(t + (tap - K/2) * dil) / up][ci], zero outside the utterance's own rows.
@@ -19,6 +22,8 @@
 //     (64 NT + (K - 1) dil of them, already upsampled, clamped, normalised and zero-padded) into LDS as
 //     fp16 hi and lo planes, each element split once; a wave then reads its B fragments with
 //     16-byte LDS reads at row (column + tap * dil).
+//     smg_conv_kernel<MT, NT, EPI_PLAIN, true> is the plain conv with another staging: a row is
+//     emb[ids[row]] + spk[spk_ids[utterance]], gathered while it is split into the planes.
 //   * Accumulator layout (16x16 tiles): lane l, register i of m-tile m holds channel 16 m + 4 (l >> 4)
 //     + i of column l & 15. The three epilogues pair m-tile m with m-tile m + MT/2 in registers.
 //
@@ -32,8 +37,10 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "../../include/pwg_embed.h"
 #include "../../include/pwg_smg.h"
 #include "pwg_internal.h"
 
@@ -54,7 +61,7 @@ struct SmgUtt {
   long long p0;  // prefix sum of n0
   long long f0;  // prefix sum of frames
   long long z0;  // prefix sum of noise_len
-  int n0;        // noise_len * noise_factor: rows at rate 1
+  int n0;        // rows at rate 1: noise_len * noise_factor, or frames in a trimmed plan
   int frames;
   int noise_len;
   int pad_;
@@ -90,6 +97,7 @@ struct NoiseArgs {
   float* out;
   int cin, cout, s, p, f_in;  // f_in: input rows per noise column
   float slope;
+  int trim;  // the last layer of a trimmed plan: rows t < n0 only, written at row p0 + t
 };
 
 __global__ __launch_bounds__(256) void smg_noise_kernel(NoiseArgs a) {
@@ -98,6 +106,7 @@ __global__ __launch_bounds__(256) void smg_noise_kernel(NoiseArgs a) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= L * a.s * a.cout) return;
   const long long t = e / a.cout;
+  if (a.trim && t >= ut.n0) return;
   const int o = (int)(e - t * a.cout);
   const long long l1 = (t + a.p) / a.s;
   const int k1 = (int)((t + a.p) - l1 * a.s);
@@ -113,7 +122,8 @@ __global__ __launch_bounds__(256) void smg_noise_kernel(NoiseArgs a) {
     const float* w = a.w + (size_t)(k1 + a.s) * a.cin * a.cout + o;
     for (int i = 0; i < a.cin; ++i) acc = fmaf(x[i], w[(size_t)i * a.cout], acc);
   }
-  a.out[(ut.z0 * a.f_in * a.s + t) * a.cout + o] = acc >= 0.f ? acc : acc * a.slope;
+  const long long row0 = a.trim ? ut.p0 : ut.z0 * a.f_in * a.s;
+  a.out[(row0 + t) * a.cout + o] = acc >= 0.f ? acc : acc * a.slope;
 }
 
 // ------------------------------------------------------------------ statistics
@@ -242,8 +252,24 @@ __device__ inline void split4(const float4 v, _Float16* hi, _Float16* lo) {
   *reinterpret_cast<f16x4*>(lo) = l;
 }
 
-template <int MT, int NT, int EPI>
-__global__ __launch_bounds__(256) void smg_conv_kernel(ConvArgs a) {
+// The token front end of the first aux conv (style_melgan.py:497-505): the staged row is
+// emb[ids[f0 + row]] + spk[spk_ids[u]], one fp32 add per element as pwg_embed_rows makes it. Every id
+// is checked before an address is formed from it; a bad one ORs its PWG_EMBED_* bit, shifted by
+// PWG_SMG_FLAG_EMBED_SHIFT, into the run's flag.
+struct TokArgs {
+  const float* emb;          // num_embs x cin
+  const float* spk;          // num_spk x cin
+  const long long* ids;      // sum frames
+  const long long* spk_ids;  // n_utts
+  int* flag;
+  int num_embs, num_spk;
+};
+
+struct NoTokArgs {};
+
+template <int MT, int NT, int EPI, bool TOK = false>
+__global__ __launch_bounds__(256) void smg_conv_kernel(ConvArgs a, std::conditional_t<TOK, TokArgs, NoTokArgs> tok) {
+  [[maybe_unused]] const auto* tk = &tok;
   extern __shared__ __attribute__((aligned(16))) unsigned char smg_smem[];
   constexpr int ROWS = 64 * NT;
   constexpr int CM = MT / 2;                         // m-tiles of one half (modulate, gate)
@@ -264,11 +290,39 @@ __global__ __launch_bounds__(256) void smg_conv_kernel(ConvArgs a) {
   {  // stage rows [t0 - halo, t0 + ROWS + halo) of the (virtual, upsampled) input
     const int c4n = a.cin >> 2;
     const long long in_row0 = a.in_is_c ? ut.f0 : ut.p0 * (a.rate / a.up);
+    long long sid = 0;
+    bool spk_ok = false;
+    if constexpr (TOK) {
+      sid = tk->spk_ids[u];
+      spk_ok = sid >= 0 && sid < tk->num_spk;
+      if (!spk_ok) {
+        sid = 0;  // never an address
+        if (threadIdx.x == 0)
+          __hip_atomic_fetch_or(tk->flag, PWG_EMBED_BAD_SPEAKER << PWG_SMG_FLAG_EMBED_SHIFT, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
     for (int idx = threadIdx.x; idx < nrow * c4n; idx += 256) {
       const int r = idx / c4n, c4 = idx - r * c4n;
       const long long tv = t0 - halo + r;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (tv >= 0 && tv < rows) {
+      if constexpr (TOK) {
+        if (tv >= 0 && tv < rows) {
+          long long pr = tv / a.up;
+          if (pr > ut.frames - 1) pr = ut.frames - 1;
+          const long long id = tk->ids[in_row0 + pr];
+          if (id >= 0 && id < tk->num_embs) {
+            v = *reinterpret_cast<const float4*>(tk->emb + id * a.cin + 4 * c4);
+            if (spk_ok) {
+              const float4 g = *reinterpret_cast<const float4*>(tk->spk + sid * a.cin + 4 * c4);
+              v = make_float4(v.x + g.x, v.y + g.y, v.z + g.z, v.w + g.w);
+            }
+          } else if (c4 == 0) {  // the row stays zero
+            __hip_atomic_fetch_or(tk->flag, PWG_EMBED_BAD_TOKEN << PWG_SMG_FLAG_EMBED_SHIFT, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+      } else if (tv >= 0 && tv < rows) {
         long long pr = tv / a.up;
         if (a.in_is_c && pr > ut.frames - 1) pr = ut.frames - 1;  // replicate pad
         v = *reinterpret_cast<const float4*>(a.in + (in_row0 + pr) * a.cin + 4 * c4);
@@ -472,7 +526,7 @@ __global__ __launch_bounds__(256) void smg_output_kernel(OutArgs a) {
   }
   const float y = tanhf(acc);
   a.out[(ut.f0 * a.hop + t) * a.oc + o] = y;
-  if (!(fabsf(y) <= 1.f)) __hip_atomic_fetch_or(a.flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!(fabsf(y) <= 1.f)) __hip_atomic_fetch_or(a.flag, PWG_SMG_FLAG_NONFINITE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------ host side
@@ -516,6 +570,7 @@ struct PwgSmg {
 struct PwgSmgPlan {
   const PwgSmg* g;
   int n_utts;
+  bool trim;  // PWG_SMG_PLAN_TRIM_NOISE
   std::vector<SmgUtt> utts;
   long long tot_n0, tot_frames, tot_z, max_n0, max_frames, max_z;
   // workspace offsets in bytes
@@ -538,7 +593,7 @@ hipError_t launch_conv_inst(const ConvArgs& a, dim3 grid, int lds, hipStream_t s
   auto kfn = smg_conv_kernel<MT, NT, EPI>;
   const hipError_t e = pwg::allow_lds(reinterpret_cast<const void*>(kfn), lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kfn, grid, dim3(256), (size_t)lds, s, a);
+  hipLaunchKernelGGL(kfn, grid, dim3(256), (size_t)lds, s, a, NoTokArgs{});
   return hipGetLastError();
 }
 
@@ -547,8 +602,34 @@ hipError_t launch_conv_nt(const ConvArgs& a, int nt, dim3 grid, int lds, hipStre
   return nt == 2 ? launch_conv_inst<MT, 2, EPI>(a, grid, lds, s) : launch_conv_inst<MT, 1, EPI>(a, grid, lds, s);
 }
 
-// mt: 16-row m-tiles of the conv's output (C / 16 plain, 2 C / 16 modulate and gate)
-hipError_t launch_conv(const ConvArgs& a, int mt, int nt, int epi, dim3 grid, int lds, hipStream_t s) {
+template <int MT, int NT>
+hipError_t launch_tok_inst(const ConvArgs& a, const TokArgs& tk, dim3 grid, int lds, hipStream_t s) {
+  auto kfn = smg_conv_kernel<MT, NT, EPI_PLAIN, true>;
+  const hipError_t e = pwg::allow_lds(reinterpret_cast<const void*>(kfn), lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kfn, grid, dim3(256), (size_t)lds, s, a, tk);
+  return hipGetLastError();
+}
+
+template <int MT>
+hipError_t launch_tok_nt(const ConvArgs& a, const TokArgs& tk, int nt, dim3 grid, int lds, hipStream_t s) {
+  return nt == 2 ? launch_tok_inst<MT, 2>(a, tk, grid, lds, s) : launch_tok_inst<MT, 1>(a, tk, grid, lds, s);
+}
+
+// mt: 16-row m-tiles of the conv's output (C / 16 plain, 2 C / 16 modulate and gate); tk: the token
+// staging of the first aux conv (plain only), or null
+hipError_t launch_conv(const ConvArgs& a, const TokArgs* tk, int mt, int nt, int epi, dim3 grid, int lds,
+                       hipStream_t s) {
+  if (tk) {
+    if (epi != EPI_PLAIN) return hipErrorInvalidValue;
+    switch (mt) {
+      case 1: return launch_tok_nt<1>(a, *tk, nt, grid, lds, s);
+      case 2: return launch_tok_nt<2>(a, *tk, nt, grid, lds, s);
+      case 3: return launch_tok_nt<3>(a, *tk, nt, grid, lds, s);
+      case 4: return launch_tok_nt<4>(a, *tk, nt, grid, lds, s);
+    }
+    return hipErrorInvalidValue;
+  }
   if (epi == EPI_PLAIN) {
     switch (mt) {
       case 1: return launch_conv_nt<1, EPI_PLAIN>(a, nt, grid, lds, s);
@@ -814,20 +895,32 @@ int pwg_smg_pack_weights(const PwgSmg* g, const float* ref, float* packed) {
 
 int pwg_smg_plan_create(const PwgSmg* g, int n_utts, const long long* frames, const long long* noise_len,
                         PwgSmgPlan** out) {
+  return pwg_smg_plan_create_ex(g, n_utts, frames, noise_len, 0, out);
+}
+
+int pwg_smg_plan_create_ex(const PwgSmg* g, int n_utts, const long long* frames, const long long* noise_len, int flags,
+                           PwgSmgPlan** out) {
   if (!g || !frames || !noise_len || !out) return set_error(PWG_ERR_INVALID, "pwg_smg_plan_create: null argument");
   *out = nullptr;
+  if (flags & ~PWG_SMG_PLAN_TRIM_NOISE) return set_error(PWG_ERR_INVALID, "pwg_smg_plan_create_ex: unknown flags");
   if (n_utts < 1 || n_utts > 65535) return set_error(PWG_ERR_INVALID, "pwg_smg_plan_create: 1 to 65535 utterances");
+  const bool trim = (flags & PWG_SMG_PLAN_TRIM_NOISE) != 0;
   PwgSmgPlan* p = new PwgSmgPlan();
   p->g = g;
   p->n_utts = n_utts;
+  p->trim = trim;
   long long p0 = 0, f0 = 0, z0 = 0, mn = 0, mf = 0, mz = 0;
   for (int u = 0; u < n_utts; ++u) {
-    const long long n0 = noise_len[u] * g->noise_factor;
+    const long long cover = noise_len[u] * g->noise_factor;
+    const long long n0 = trim ? frames[u] : cover;
     const char* err = nullptr;
     if (frames[u] < 1) err = "pwg_smg_plan_create: every utterance needs at least one frame";
-    else if (noise_len[u] < 1 || n0 < frames[u])
+    else if (trim && frames[u] < 2)
+      err = "pwg_smg_plan_create_ex: a trimmed plan needs at least two frames per utterance (instance norm over one "
+            "row is undefined; the reference raises)";
+    else if (noise_len[u] < 1 || cover < frames[u])
       err = "pwg_smg_plan_create: noise_len * noise_upsample_factor must cover the utterance's frames";
-    else if (n0 * g->hop > (1LL << 30)) err = "pwg_smg_plan_create: utterance too long";
+    else if (cover * g->hop > (1LL << 30)) err = "pwg_smg_plan_create: utterance too long";
     if (err) {
       delete p;
       return set_error(PWG_ERR_INVALID, err);
@@ -847,8 +940,11 @@ int pwg_smg_plan_create(const PwgSmg* g, int n_utts, const long long* frames, co
   p->ws_flag = take(256);
   const long long big = p0 * g->hop * C * 4;  // one tensor at the final rate
   p->ws_partial = take((p0 * g->hop / 64 + n_utts + 1) * C * 8);
-  p->ws_noise[0] = take(p0 * C * 4);
-  p->ws_noise[1] = take(p0 * C * 4);
+  // the noise layers before the last: noise_len * (product of all but the last scale) rows each, which is
+  // at most p0 rows only while p0 == tot_z * noise_factor
+  const long long mid_rows = trim ? z0 * (g->noise_factor / g->cfg.noise_scales[g->cfg.num_noise_scales - 1]) : p0;
+  p->ws_noise[0] = take(mid_rows * C * 4);
+  p->ws_noise[1] = take(mid_rows * C * 4);
   for (int b = 0; b <= g->nblocks; ++b) p->ws_x.push_back(take(p0 * p->rate[b] * C * 4));
   for (int i = 0; i <= 2 * g->nblocks; ++i) p->ws_stats.push_back(take((long long)n_utts * C * 8));
   p->ws_c1 = take(big);
@@ -884,17 +980,11 @@ int pwg_smg_plan_tensor(const PwgSmgPlan* p, int block, int which, long long* of
   return set_error(PWG_ERR_INVALID, "pwg_smg_plan_tensor: no such tensor");
 }
 
-int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const float* mean, const float* scale,
-                const float* z, float* out, void* workspace, void* stream) {
-  if (!p || !packed || !c || !z || !out || !workspace) return set_error(PWG_ERR_INVALID, "pwg_smg_run: null argument");
-  if ((mean == nullptr) != (scale == nullptr)) return set_error(PWG_ERR_INVALID, "pwg_smg_run: mean and scale go together");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return set_error(PWG_ERR_INVALID, "pwg_smg_run: workspace must be 256-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(mean) |
-       reinterpret_cast<uintptr_t>(scale)) & 15)
-    return set_error(PWG_ERR_INVALID, "pwg_smg_run: packed, c, mean and scale must be 16-byte aligned");
+// The launches of pwg_smg_run (c, with mean and scale or without) and of pwg_smg_run_tokens (tok; its flag
+// pointer is filled in here). The callers have checked their arguments.
+static int run_launches(const PwgSmgPlan* p, const float* packed, const float* c, const float* mean, const float* scale,
+                        const TokArgs* tok, const float* z, float* out, void* workspace, void* stream) {
   PwgSmg* g = const_cast<PwgSmg*>(p->g);
-  if (g->device < 0) return set_error(PWG_ERR_INVALID, "pwg_smg_run: a host-only handle cannot run");
-  if (const int rc = check_device(g->device, "pwg_smg_run")) return rc;
   const PwgSmgConfig& cf = g->cfg;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
@@ -906,6 +996,11 @@ int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const 
   const hipError_t e = upload_table(p->utts, reinterpret_cast<SmgUtt*>(ws + p->ws_utt), flag, s);
   if (e != hipSuccess) return hipf(e, "pwg_smg_run: plan upload");
   Runner r{g, s};
+  TokArgs tk{};
+  if (tok) {
+    tk = *tok;
+    tk.flag = flag;
+  }
 
   // noise upsampling: z -> x0
   const float* nin = z;
@@ -913,9 +1008,12 @@ int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const 
   for (size_t i = 0; i < g->noise.size() && r.rc == PWG_OK; ++i) {
     const ConvSpec& cs = g->noise[i];
     const int sc = cf.noise_scales[i];
-    float* nout = i + 1 == g->noise.size() ? F(p->ws_x[0]) : F(p->ws_noise[i & 1]);
-    NoiseArgs a{utt, nin, packed + cs.pk_w, packed + cs.pk_b, nout, cs.cin, cs.cout, sc, sc / 2 + sc % 2, f_in, cf.noise_slope};
-    const long long elems = p->max_z * f_in * sc * cs.cout;
+    const bool last = i + 1 == g->noise.size();
+    float* nout = last ? F(p->ws_x[0]) : F(p->ws_noise[i & 1]);
+    const int trim = last && p->trim;
+    NoiseArgs a{utt, nin, packed + cs.pk_w, packed + cs.pk_b, nout, cs.cin, cs.cout, sc, sc / 2 + sc % 2, f_in, cf.noise_slope,
+                trim};
+    const long long elems = (trim ? p->max_n0 : p->max_z * f_in * sc) * cs.cout;
     r.begin(PWG_SMG_KIND_NOISE);
     hipLaunchKernelGGL(smg_noise_kernel, dim3((unsigned)((elems + 255) / 256), (unsigned)n), dim3(256), 0, s, a);
     r.end(hipGetLastError(), "noise upsampling kernel");
@@ -937,7 +1035,7 @@ int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const 
     a.gate = cf.gate;
     const int rows = 64 * nt;
     r.begin(kind);
-    r.end(launch_conv(a, cs.mt, nt, epi, dim3((unsigned)((max_rows + rows - 1) / rows), (unsigned)n),
+    r.end(launch_conv(a, in_is_c && tok ? &tk : nullptr, cs.mt, nt, epi, dim3((unsigned)((max_rows + rows - 1) / rows), (unsigned)n),
                       conv_lds_bytes(cs.cin, K, dil, nt, epi, C), s),
           "conv kernel");
     return 64;  // rows per statistics partial
@@ -980,6 +1078,39 @@ int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const 
   return r.rc;
 }
 
+int pwg_smg_run(const PwgSmgPlan* p, const float* packed, const float* c, const float* mean, const float* scale,
+                const float* z, float* out, void* workspace, void* stream) {
+  if (!p || !packed || !c || !z || !out || !workspace) return set_error(PWG_ERR_INVALID, "pwg_smg_run: null argument");
+  if ((mean == nullptr) != (scale == nullptr)) return set_error(PWG_ERR_INVALID, "pwg_smg_run: mean and scale go together");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return set_error(PWG_ERR_INVALID, "pwg_smg_run: workspace must be 256-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(mean) |
+       reinterpret_cast<uintptr_t>(scale)) & 15)
+    return set_error(PWG_ERR_INVALID, "pwg_smg_run: packed, c, mean and scale must be 16-byte aligned");
+  if (p->g->device < 0) return set_error(PWG_ERR_INVALID, "pwg_smg_run: a host-only handle cannot run");
+  if (const int rc = check_device(p->g->device, "pwg_smg_run")) return rc;
+  return run_launches(p, packed, c, mean, scale, nullptr, z, out, workspace, stream);
+}
+
+int pwg_smg_run_tokens(const PwgSmgPlan* p, const float* packed, const float* emb, int num_embs, const float* spk,
+                       int num_spk, const long long* ids, const long long* spk_ids, const float* z, float* out,
+                       void* workspace, void* stream) {
+  if (!p || !packed || !emb || !spk || !ids || !spk_ids || !z || !out || !workspace)
+    return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: null argument");
+  if (num_embs < 1 || num_spk < 1) return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: empty embedding table");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255)
+    return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: workspace must be 256-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(emb) | reinterpret_cast<uintptr_t>(spk)) & 15)
+    return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: packed, emb and spk must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(spk_ids)) & 7)
+    return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: ids and spk_ids must be 8-byte aligned");
+  if (!p->trim)
+    return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: the plan was not created with PWG_SMG_PLAN_TRIM_NOISE");
+  if (p->g->device < 0) return set_error(PWG_ERR_INVALID, "pwg_smg_run_tokens: a host-only handle cannot run");
+  if (const int rc = check_device(p->g->device, "pwg_smg_run_tokens")) return rc;
+  const TokArgs tok{emb, spk, ids, spk_ids, nullptr, num_embs, num_spk};
+  return run_launches(p, packed, nullptr, nullptr, nullptr, &tok, z, out, workspace, stream);
+}
+
 int pwg_smg_run_status(const PwgSmgPlan* p, void* workspace, void* stream) {
   if (!p || !workspace) return set_error(PWG_ERR_INVALID, "pwg_smg_run_status: null argument");
   int flag = 0;
@@ -987,6 +1118,14 @@ int pwg_smg_run_status(const PwgSmgPlan* p, void* workspace, void* stream) {
   hipError_t e = hipMemcpyAsync(&flag, static_cast<char*>(workspace) + p->ws_flag, sizeof(int), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return hipf(e, "pwg_smg_run_status");
+  if (flag & ~PWG_SMG_FLAG_NONFINITE) {
+    const int bits = flag >> PWG_SMG_FLAG_EMBED_SHIFT;
+    const bool tokb = bits & PWG_EMBED_BAD_TOKEN, spkb = bits & PWG_EMBED_BAD_SPEAKER;
+    return set_error(PWG_ERR_RANGE, tokb && spkb ? "bad token id and bad speaker id: ids outside [0, num_embs) and [0, num_spk) "
+                                                   "were read as zero rows"
+                                    : tokb       ? "bad token id: an id outside [0, num_embs) was read as a zero row"
+                                                 : "bad speaker id: an id outside [0, num_spk) contributed zero");
+  }
   if (flag != 0)
     return set_error(PWG_ERR_RANGE,
                      "non-finite StyleMelGAN output: a value left the fp16 pair range of the split-f16 conv kernels "

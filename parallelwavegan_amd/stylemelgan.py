@@ -73,10 +73,12 @@ def make_smg_config(in_channels, aux_channels, channels, out_channels, kernel_si
 
 
 class SmgPlan:
-    """pwg_smg_plan_*: the ragged batch's layout (host only)."""
+    """pwg_smg_plan_*: the ragged batch's layout (host only). flags None: pwg_smg_plan_create; an int:
+    pwg_smg_plan_create_ex (``_lib.PWG_SMG_PLAN_TRIM_NOISE``: the token class's trimmed layout)."""
 
-    def __init__(self, handle, frames, noise_len):
+    def __init__(self, handle, frames, noise_len, flags=None):
         self.handle = handle  # keeps the PwgSmg alive
+        self.flags = flags
         self.frames = [int(f) for f in frames]
         self.noise_len = [int(n) for n in noise_len]
         n = len(self.frames)
@@ -85,8 +87,12 @@ class SmgPlan:
         ll = ctypes.c_longlong * n
         self._p = ctypes.c_void_p()
         self._lib = _lib.load()
-        _lib.check(self._lib.pwg_smg_plan_create(handle._h, n, ll(*self.frames), ll(*self.noise_len),
-                                                 ctypes.byref(self._p)))
+        if flags is None:
+            _lib.check(self._lib.pwg_smg_plan_create(handle._h, n, ll(*self.frames), ll(*self.noise_len),
+                                                     ctypes.byref(self._p)))
+        else:
+            _lib.check(self._lib.pwg_smg_plan_create_ex(handle._h, n, ll(*self.frames), ll(*self.noise_len), int(flags),
+                                                        ctypes.byref(self._p)))
         self.workspace_bytes = int(self._lib.pwg_smg_plan_workspace_bytes(self._p))
         self.out_rows = int(self._lib.pwg_smg_plan_out_rows(self._p))
 
@@ -147,14 +153,17 @@ class SmgHandle:
     def load_state_dict(self, state):
         self.packed = torch.from_numpy(self.pack(state)).to(self.device)
 
-    def plan(self, frames, noise_len):
-        return SmgPlan(self, frames, noise_len)
+    def plan(self, frames, noise_len, flags=None):
+        return SmgPlan(self, frames, noise_len, flags)
 
     def workspace(self, nbytes):
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def release_workspace(self):
+        self._ws = None
 
     def set_timing(self, on):
         _lib.check(self._lib.pwg_smg_set_timing(self._h, int(bool(on))))
@@ -174,10 +183,32 @@ class SmgHandle:
                                          scale.data_ptr() if scale is not None else None, z.data_ptr(),
                                          out.data_ptr(), ws.data_ptr(), stream))
         if check:
-            rc = self._lib.pwg_smg_run_status(plan._p, ws.data_ptr(), stream)
-            if rc == _lib.PWG_ERR_RANGE:
-                raise FloatingPointError(self._lib.pwg_last_error().decode(errors="replace"))
-            _lib.check(rc)
+            self._status(plan, ws, stream)
+        return ws
+
+    def _status(self, plan, ws, stream):
+        rc = self._lib.pwg_smg_run_status(plan._p, ws.data_ptr(), stream)
+        if rc == _lib.PWG_ERR_RANGE:
+            msg = self._lib.pwg_last_error().decode(errors="replace")
+            # (include/pwg_smg.h: an id outside its table, reported ahead of a non-finite sample)
+            raise (ValueError if msg.startswith("bad ") else FloatingPointError)(msg)
+        _lib.check(rc)
+
+    def run_tokens(self, plan, emb, spk, ids, spk_ids, z, out, check=True):
+        """pwg_smg_run_tokens on a trimmed plan. emb (num_embs, aux), spk (num_spk, aux): contiguous fp32;
+        ids (sum frames,), spk_ids (n_utts,): contiguous int64; z, out as ``run``; all on the device.
+        Returns the workspace tensor. An id outside its table raises ValueError."""
+        for t, dt in ((emb, torch.float32), (spk, torch.float32), (ids, torch.int64), (spk_ids, torch.int64)):
+            assert t.is_contiguous() and t.dtype == dt and t.device == self.packed.device
+        assert ids.numel() == sum(plan.frames) and spk_ids.numel() == len(plan.frames)
+        assert emb.shape[1] == spk.shape[1] == self.cfg.aux_channels
+        ws = self.workspace(plan.workspace_bytes)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.pwg_smg_run_tokens(plan._p, self.packed.data_ptr(), emb.data_ptr(), emb.shape[0],
+                                                spk.data_ptr(), spk.shape[0], ids.data_ptr(), spk_ids.data_ptr(),
+                                                z.data_ptr(), out.data_ptr(), ws.data_ptr(), stream))
+        if check:
+            self._status(plan, ws, stream)
         return ws
 
 

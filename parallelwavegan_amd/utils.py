@@ -19,11 +19,13 @@ import torch
 import yaml
 
 GENERATORS = ("ParallelWaveGANGenerator", "MelGANGenerator", "HiFiGANGenerator", "DiscreteSymbolHiFiGANGenerator",
-              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator", "UHiFiGANGenerator", "VQVAE")
+              "DiscreteSymbolDurationGenerator", "DiscreteSymbolF0Generator", "UHiFiGANGenerator", "VQVAE",
+              "DiscreteSymbolStyleMelGANGenerator")
 
 
 def generator_class(name):
     from .dsym import DiscreteSymbolHiFiGANGenerator
+    from .dsym_stylemelgan import DiscreteSymbolStyleMelGANGenerator
     from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator
     from .hifigan import HiFiGANGenerator
     from .melgan import MelGANGenerator
@@ -36,7 +38,7 @@ def generator_class(name):
              "DiscreteSymbolHiFiGANGenerator": DiscreteSymbolHiFiGANGenerator,
              "DiscreteSymbolDurationGenerator": DiscreteSymbolDurationGenerator,
              "DiscreteSymbolF0Generator": DiscreteSymbolF0Generator, "UHiFiGANGenerator": UHiFiGANGenerator,
-             "VQVAE": VQVAE}
+             "VQVAE": VQVAE, "DiscreteSymbolStyleMelGANGenerator": DiscreteSymbolStyleMelGANGenerator}
     if name not in table:
         raise NotImplementedError(f"generator_type {name!r} is not accelerated (supported: {', '.join(GENERATORS)})")
     return table[name]
@@ -73,7 +75,9 @@ def load_model(checkpoint, config=None, stats=None):
         cand = os.path.join(os.path.dirname(checkpoint), f"stats.{ext}")
         if os.path.exists(cand):
             stats = cand
-    if stats is not None and generator_type != "VQVAE":  # (utils/utils.py:343: a VQVAE takes no feature stats)
+    # (utils/utils.py:343: a VQVAE takes no feature stats; nor does the token StyleMelGAN, which has no
+    # register_stats in the reference)
+    if stats is not None and generator_type not in ("VQVAE", "DiscreteSymbolStyleMelGANGenerator"):
         model.register_stats(stats)
     if config["generator_params"].get("out_channels", 1) > 1:
         from .melgan import PQMF
