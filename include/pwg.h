@@ -248,11 +248,16 @@ enum {
                                     launch give up at once (its workgroups run ahead on partial
                                     planes, status bit 8, NaN audio, PWG_ERR_RERUN from
                                     pwg_run_status); default 0 */
-  PWG_OPT_FRAGMENT_AHEAD = 9   /* split16 per-layer launches: 1 takes the kernels that read each
+  PWG_OPT_FRAGMENT_AHEAD = 9,  /* split16 per-layer launches: 1 takes the kernels that read each
                                     MFMA step's weight fragments from LDS one step ahead, with
                                     counted waits (default); 0 the kernels that leave the reads to the
                                     compiler. Bit-identical. The grid-synchronised and pipelined
                                     launches have the second form only. */
+  PWG_OPT_SKIP_AHEAD = 10      /* split16 per-layer launches in the PWG_OPT_FRAGMENT_AHEAD form: 1
+                                    (default) takes the kernels that request a block's old skip sums
+                                    before the center tap's MFMAs, a tap ahead of GEMM 2; 0 the
+                                    kernels that request them after GEMM 1. Bit-identical; no effect
+                                    with PWG_OPT_FRAGMENT_AHEAD at 0. */
 };
 #define PWG_PIPE_MAX_DEFAULT 0LL /* off: measured slower than the per-layer launches */
 PWG_API int pwg_set_option(PwgHandle* h, int option, long long value);

@@ -163,6 +163,7 @@ PWG_OPT_SYNC = 6
 PWG_OPT_SYNC_ABORT = 7
 PWG_OPT_SYNC_TIMEOUT = 8
 PWG_OPT_FRAGMENT_AHEAD = 9
+PWG_OPT_SKIP_AHEAD = 10
 
 
 PWG_VQ_BAD_CODE, PWG_VQ_BAD_GLOBAL, PWG_VQ_BAD_INPUT = 1, 2, 4

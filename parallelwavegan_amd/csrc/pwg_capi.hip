@@ -378,6 +378,7 @@ struct PwgHandle {
   int sync_abort = 0;       // PWG_OPT_SYNC_ABORT (test hook)
   int sync_timeout = 0;     // PWG_OPT_SYNC_TIMEOUT (test hook)
   int frag_ahead = 1;       // PWG_OPT_FRAGMENT_AHEAD
+  int skip_ahead = 1;       // PWG_OPT_SKIP_AHEAD
   long long fa_launches = 0;  // pwg_fragment_ahead_launches: launches of the last run in that form
   long long sync_max = -1;  // PWG_OPT_SYNC: most 32-sample blocks on the grid-synchronised forward (-1: 64 x n_cu)
   long long half_max = -1;  // PWG_OPT_HALF_BLOCKS: most blocks of a half-block launch (-1: 4 x n_cu)
@@ -1330,8 +1331,9 @@ static int pwg_run_impl(PwgPlan* p, const float* packed, const float* mel, const
       const bool frag_ahead =
           split16 && h->frag_ahead && split16_has_fragment_ahead(last, sa.noise != nullptr, half);
       if (frag_ahead) ++h->fa_launches;
+      const bool skip_ahead = frag_ahead && h->skip_ahead;
       e = timed(PWG_KERNEL_RESIDUAL_LAYER, [&] {
-        return split16 ? launch_layer_split16(sa, last, la.tap_center, launch_w, nwg, s, half, frag_ahead)
+        return split16 ? launch_layer_split16(sa, last, la.tap_center, launch_w, nwg, s, half, frag_ahead, skip_ahead)
                        : launch_layer_split(sa, last, la.tap_center, wpw, nwg, s);
       });
       if (e == hipSuccess && last && trace_on) {
@@ -1536,6 +1538,10 @@ int pwg_set_option(PwgHandle* h, int option, long long value) {
       if (value != 0 && value != 1) return fail(PWG_ERR_INVALID, "fragment_ahead must be 0 or 1");
       h->frag_ahead = (int)value;
       return PWG_OK;
+    case PWG_OPT_SKIP_AHEAD:
+      if (value != 0 && value != 1) return fail(PWG_ERR_INVALID, "skip_ahead must be 0 or 1");
+      h->skip_ahead = (int)value;
+      return PWG_OK;
 
     default:
       return fail(PWG_ERR_INVALID, "unknown option");
@@ -1555,6 +1561,7 @@ int pwg_get_option(const PwgHandle* h, int option, long long* value) {
     case PWG_OPT_SYNC_ABORT: *value = h->sync_abort; return PWG_OK;
     case PWG_OPT_SYNC_TIMEOUT: *value = h->sync_timeout; return PWG_OK;
     case PWG_OPT_FRAGMENT_AHEAD: *value = h->frag_ahead; return PWG_OK;
+    case PWG_OPT_SKIP_AHEAD: *value = h->skip_ahead; return PWG_OK;
 
     default: return fail(PWG_ERR_INVALID, "unknown option");
   }

@@ -284,9 +284,10 @@ hipError_t launch_layer(const LayerArgs& a, int mt, int m2t, bool last, long lon
 hipError_t launch_first_conv_split(const FirstConvArgs& a, long long n_tiles, hipStream_t s);
 hipError_t launch_first_conv_split16(const FirstConvArgs& a, long long n_tiles, hipStream_t s);
 // frag_ahead: the kernel form that reads its A fragments a step ahead of their MFMAs
-// (PWG_OPT_FRAGMENT_AHEAD); only for the roles split16_has_fragment_ahead names
+// (PWG_OPT_FRAGMENT_AHEAD); only for the roles split16_has_fragment_ahead names. skip_ahead: that
+// form with the block's skip seeds loaded a tap ahead (PWG_OPT_SKIP_AHEAD); needs frag_ahead
 hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, int waves_per_wg, int n_wg,
-                                hipStream_t s, bool half = false, bool frag_ahead = false);
+                                hipStream_t s, bool half = false, bool frag_ahead = false, bool skip_ahead = false);
 bool split16_has_fragment_ahead(bool last, bool first, bool half);
 hipError_t launch_layer_split(const SplitArgs& a, bool last, int tap_center, int waves_per_wg, int n_wg,
                               hipStream_t s);

@@ -34,7 +34,9 @@ __device__ __forceinline__ f32x4 mma16(u32x4 a, u32x4 b, f32x4 c) {
                                                 0);
 }
 
-// rows pre-scaled into exp2 arguments (see pwg_split.hip gate())
+// rows pre-scaled into exp2 arguments (see pwg_split.hip gate()). Kept per value: written on
+// 2-vectors (packed fp32 multiplies and subtracts, 48 fewer VALU per block) it measured 0.1-0.6 %
+// slower.
 __device__ __forceinline__ float gate16(float u, float v) {
   u = fminf(u, 64.f);
   const float e1 = __builtin_amdgcn_exp2f(u);
@@ -337,20 +339,36 @@ __device__ __forceinline__ void s16_load_dv(const SplitArgs& a, const BlockDesc&
 }
 
 // The old skip sum of a block as GEMM-2 seeds sk[ms][nt] (skip rows 16 ms + 4 g + i of column
-// bd.col + 16 nt + c). Layer 0: the sum of all layers' skip biases.
-template <bool PIPE, int NTN = 2>
+// bd.col + 16 nt + c). Layer 0: the sum of all layers' skip biases. ONE: a.first (wave-uniform)
+// is tested once around all the loads instead of once per load.
+template <bool PIPE, int NTN = 2, bool ONE = false>
 __device__ __forceinline__ void s16_load_skip(const SplitArgs& a, const BlockDesc& bd, f32x4 (&sk)[4][2], int g,
                                               int c, int h16 = 0) {
   const Plane16<PIPE> skip(a.skip);
   const long long sb = (long long)((bd.col + h16) >> 4) * 4096;
   const unsigned vo = 16u * (unsigned)(16 * g + c);
+  if constexpr (ONE) {
+    if (a.first) {
 #pragma unroll
-  for (int nt = 0; nt < NTN; ++nt)
+      for (int nt = 0; nt < NTN; ++nt)
 #pragma unroll
-    for (int ms = 0; ms < 4; ++ms) {
-      if (a.first) sk[ms][nt] = reinterpret_cast<const f32x4*>(a.skip0 + 16 * g)[ms];
-      else sk[ms][nt] = __builtin_bit_cast(f32x4, skip.template load<true>(sb + nt * 4096, vo, ms * 1024));
+        for (int ms = 0; ms < 4; ++ms) sk[ms][nt] = reinterpret_cast<const f32x4*>(a.skip0 + 16 * g)[ms];
+    } else {
+#pragma unroll
+      for (int nt = 0; nt < NTN; ++nt)
+#pragma unroll
+        for (int ms = 0; ms < 4; ++ms)
+          sk[ms][nt] = __builtin_bit_cast(f32x4, skip.template load<true>(sb + nt * 4096, vo, ms * 1024));
     }
+  } else {
+#pragma unroll
+    for (int nt = 0; nt < NTN; ++nt)
+#pragma unroll
+      for (int ms = 0; ms < 4; ++ms) {
+        if (a.first) sk[ms][nt] = reinterpret_cast<const f32x4*>(a.skip0 + 16 * g)[ms];
+        else sk[ms][nt] = __builtin_bit_cast(f32x4, skip.template load<true>(sb + nt * 4096, vo, ms * 1024));
+      }
+  }
 }
 
 // One 32-sample block of one WaveNet residual block (layers/residual_block.py:102-140) with the
@@ -372,11 +390,13 @@ __device__ __forceinline__ void s16_load_skip(const SplitArgs& a, const BlockDes
 // FA: the A fragments of GEMM 1 and GEMM 2 are read one (ks, m) step ahead of their MFMAs into
 // two rotating slots (fa_read / fa_wait above), across tap boundaries and from the end of GEMM 1
 // into GEMM 2. Same MFMAs in the same order per accumulator: bit-identical to !FA.
-template <bool LAST, int TC, bool FIRST, bool PIPE, int NTN = 2, bool AL = false, bool FA = false, typename Mid>
+template <bool LAST, int TC, bool FIRST, bool PIPE, int NTN = 2, bool AL = false, bool FA = false, bool SA = false,
+          typename Mid>
 __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* smem16, const BlockDesc& bd_v,
                                           const BlockDesc& bdn_v, bool has_next, u32x4 (&b0)[8], u32x4 (&b1)[8],
                                           bool& nonfinite, Mid&& mid, int h16_v = 0, int h16n_v = 0,
                                           bool poison = false) {
+  static_assert(!SA || FA, "the skip-ahead form builds on the read-ahead body");
   static_assert(NTN == 2 || !LAST, "half blocks: middle layers");
   const BlockDesc bd = uniform_desc(bd_v);
   const int h16 = NTN == 1 ? __builtin_amdgcn_readfirstlane(h16_v) : 0;
@@ -495,6 +515,7 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt) acc[m][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
   f32x4 acc2[8][2];
+  f32x4 sk[4][2];  // skip seeds: the old skip sum
   if constexpr (FA) fa_read<0>(fh[0], fl[0], fa_base);
   s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bd, T1, b1, g, c, h16);
   if constexpr (FA) mma_tap_fa(acc, b0, 0, T1);
@@ -503,6 +524,9 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
   s16_bload<TC, FIRST, PIPE, NTN, AL>(a, s_fwb, bd, TC, b0, g, c, h16);
   if constexpr (FA) {
     mma_tap_fa(acc, b1, T1, TC);
+    // SA: the skip loads (always HBM misses) go out here, a whole tap of MFMAs, the aux term and
+    // the gate ahead of GEMM 2's first MFMA; the T1 row's 32 registers died with the step above
+    if constexpr (SA) s16_load_skip<PIPE, NTN, true>(a, bd, sk, g, c, h16);
     mma_tap_fa(acc, b0, TC, 3);  // its last step issues GEMM 2's first pair, in flight through the gate
   } else {
     mma_tap(acc, b1, T1);
@@ -524,9 +548,8 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
   mid();
 
   {
-    // skip seeds: old skip sum, in flight during the aux term and the gate
-    f32x4 sk[4][2];
-    s16_load_skip<PIPE, NTN>(a, bd, sk, g, c, h16);
+    // skip seeds, in flight during the aux term and the gate unless they were loaded a tap ahead
+    if constexpr (!SA) s16_load_skip<PIPE, NTN>(a, bd, sk, g, c, h16);
 #pragma unroll
     for (int nt = 0; nt < NTN; ++nt)
 #pragma unroll
@@ -743,10 +766,11 @@ __device__ __forceinline__ void s16_block(const SplitArgs& a, const unsigned* sm
 // n-tile; unit u = block u / 2, columns 16 (u % 2) + [0, 16)), so twice the waves share a layer and
 // each wave's dependent chain runs half the MFMAs; bit-identical to whole blocks.
 // AL: the layer's dilation is a multiple of 16 (s16_bload; the host knows it). FA: the block body
-// reads its A fragments a step ahead (s16_block; PWG_OPT_FRAGMENT_AHEAD). NTN stays the last
+// reads its A fragments a step ahead (s16_block; PWG_OPT_FRAGMENT_AHEAD). SA: that body requests
+// the skip seeds before the center tap (s16_block; PWG_OPT_SKIP_AHEAD). NTN stays the last
 // template argument: bench.py tells the kernels apart by their names, where a name ending in
 // ", true>" does not count as a middle layer.
-template <bool LAST, int TC, bool FIRST, bool AL, bool FA, int NTN>
+template <bool LAST, int TC, bool FIRST, bool AL, bool FA, bool SA, int NTN>
 __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitArgs a) {
   constexpr int UB = NTN == 1 ? 1 : 0;  // log2(units per block)
   const int n_units = a.n_blocks << UB;
@@ -845,7 +869,7 @@ __global__ void __launch_bounds__(512, 1) pwg_layer_split16_kernel(const SplitAr
     bdn = a.blocks[pf >> UB];
     h16n = NTN == 1 ? 16 * (pf & 1) : 0;
     int ticket = 0;
-    s16_block<LAST, TC, FIRST, false, NTN, AL, FA>(a, smem16, bd, bdn, true, b0, b1, nonfinite, [&]() {
+    s16_block<LAST, TC, FIRST, false, NTN, AL, FA, SA>(a, smem16, bd, bdn, true, b0, b1, nonfinite, [&]() {
       if (nblk >= 0) ticket = ticket_issue();
     }, h16, h16n, poison);
     if (tr && n_done++ == 0) t_first = __builtin_amdgcn_s_memrealtime();
@@ -1153,15 +1177,15 @@ bool split16_has_fragment_ahead(bool last, bool first, bool half) {
 }
 
 hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, int waves_per_wg, int n_wg,
-                                hipStream_t s, bool half, bool frag_ahead) {
+                                hipStream_t s, bool half, bool frag_ahead, bool skip_ahead) {
   if (waves_per_wg > 8) waves_per_wg = 8;
   if (a.compute_waves < 1 || a.compute_waves > waves_per_wg) return hipErrorInvalidValue;
   if (half && last) return hipErrorInvalidValue;  // the head needs both n-tiles of a block
   const dim3 grid((unsigned)n_wg), block((unsigned)(64 * waves_per_wg));
-#define PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, FA_)                                       \
+#define PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, FA_, SA_)                                  \
   {                                                                                                     \
     const size_t lds = sizeof(unsigned) * (Split16Smem::dwords(LAST_) + (FIRST_ ? 128 : 0));            \
-    auto kfn = &pwg_layer_split16_kernel<LAST_, TC_, FIRST_, AL_, FA_, NTN_>;                           \
+    auto kfn = &pwg_layer_split16_kernel<LAST_, TC_, FIRST_, AL_, FA_, SA_, NTN_>;                      \
     hipError_t e_ = allow_lds(reinterpret_cast<const void*>(kfn), (int)lds);                           \
     if (e_ != hipSuccess) return e_;                                                                    \
     hipLaunchKernelGGL(kfn, grid, block, lds, s, a);                                                    \
@@ -1170,12 +1194,16 @@ hipError_t launch_layer_split16(const SplitArgs& a, bool last, int tap_center, i
 #define PWG_SPLIT16_LAUNCH(LAST_, TC_, FIRST_, NTN_, AL_)                                               \
   {                                                                                                     \
     if constexpr (LAST_ ? FA_LAST : FIRST_ ? (NTN_ == 1 ? FA_FIRST_HALF : FA_FIRST_WHOLE) : FA_MIDDLE) \
-      if (frag_ahead) PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, true)                        \
-    PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, false)                                         \
+      if (frag_ahead) {                                                                                 \
+        if (skip_ahead) PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, true, true)                \
+        PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, true, false)                               \
+      }                                                                                                 \
+    PWG_SPLIT16_LAUNCH_FA(LAST_, TC_, FIRST_, NTN_, AL_, false, false)                                  \
   }
   const bool first = a.noise != nullptr;  // fused first_conv (never together with last: L > 1)
   if (first && last) return hipErrorInvalidValue;
   if (frag_ahead && !split16_has_fragment_ahead(last, first, half)) return hipErrorInvalidValue;
+  if (skip_ahead && !frag_ahead) return hipErrorInvalidValue;  // built on the read-ahead body only
   // middle layers: taps shifted by a multiple of 16 columns keep the constant lane offset
   const bool al = a.dil % 16 == 0;
 #define PWG_SPLIT16_MIDDLE(TC_, NTN_) \

@@ -418,7 +418,7 @@ class Engine:
 
     def set_option(self, option, value):
         """pwg_set_option: option in {"layer_kernel", "waves_per_wg", "wg_per_cu", "fuse_first_conv",
-        "pipeline", "half_blocks", "sync", "fragment_ahead"}. "pipeline" (largest padded plan on the layer-pipelined launch, 0 = never)
+        "pipeline", "half_blocks", "sync", "fragment_ahead", "skip_ahead"}. "pipeline" (largest padded plan on the layer-pipelined launch, 0 = never)
         applies to plans created afterwards: the cached plans are dropped."""
         opts = self._OPTS
         if option == "layer_kernel" and isinstance(value, str):
@@ -435,7 +435,8 @@ class Engine:
              "wg_per_cu": _lib.PWG_OPT_WG_PER_CU, "fuse_first_conv": _lib.PWG_OPT_FUSE_FIRST_CONV,
              "pipeline": _lib.PWG_OPT_PIPELINE, "half_blocks": _lib.PWG_OPT_HALF_BLOCKS,
              "sync": _lib.PWG_OPT_SYNC, "sync_abort": _lib.PWG_OPT_SYNC_ABORT,
-             "sync_timeout": _lib.PWG_OPT_SYNC_TIMEOUT, "fragment_ahead": _lib.PWG_OPT_FRAGMENT_AHEAD}
+             "sync_timeout": _lib.PWG_OPT_SYNC_TIMEOUT, "fragment_ahead": _lib.PWG_OPT_FRAGMENT_AHEAD,
+             "skip_ahead": _lib.PWG_OPT_SKIP_AHEAD}
     SYNC_FAIL_STREAK = 3
     SYNC_RETRY_RUNS = 256
 
