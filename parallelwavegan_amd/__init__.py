@@ -15,6 +15,9 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
                             noise trimmed to the frames (pwg_smg_plan_create_ex, pwg_smg_run_tokens)
   UHiFiGANGenerator         drop-in U-Net HiFiGAN (mel + excitation): HIP excitation front end, strided
                             and two-source transposed convs on the conv-network executor
+  SineGen                   drop-in sine excitation generator (layers/sine.py): f0 -> sine, uv, noise with
+                            an exact 64-bit integer phase (include/pwg_sine.h); feeds UHiFiGANGenerator's
+                            *_from_f0 methods
   VQVAE                     drop-in VQ-VAE (waveform -> codes -> waveform): HIP grouped strided encoder
                             levels, nearest-code search and decoder front end (include/pwg_vq.h)
 """
@@ -24,6 +27,7 @@ from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
 from .dsym_stylemelgan import DiscreteSymbolStyleMelGANGenerator  # noqa: F401
 from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator  # noqa: F401
 from .models import ParallelWaveGANGenerator  # noqa: F401
+from .sinegen import SineGen  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401
 from .uhifigan import UHiFiGANGenerator  # noqa: F401
 from .vqvae import VQVAE  # noqa: F401

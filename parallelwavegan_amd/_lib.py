@@ -32,11 +32,13 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_smg.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_uconv.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_vq.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_sine.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
     os.path.join(REPO_DIR, "include", "pwg_cnet.h"),
     os.path.join(REPO_DIR, "include", "pwg_embed.h"),
+    os.path.join(REPO_DIR, "include", "pwg_sine.h"),
     os.path.join(REPO_DIR, "include", "pwg_smg.h"),
     os.path.join(REPO_DIR, "include", "pwg_uhg.h"),
     os.path.join(REPO_DIR, "include", "pwg_vq.h"),
@@ -124,6 +126,11 @@ EXPORTED_SYMBOLS = (
     "pwg_embed_rows_f0",
     # include/pwg_uhg.h: UHiFiGAN's excitation front end (csrc/pwg_uconv.hip)
     "pwg_uhg_excite_rows",
+    # include/pwg_sine.h: sine excitation from f0 (csrc/pwg_sine.hip)
+    "pwg_sine_scratch_bytes",
+    "pwg_sine_frames_scratch_bytes",
+    "pwg_sine_samples",
+    "pwg_sine_frames",
     # include/pwg_vq.h: VQVAE's encoder front end, grouped strided levels, code search and decoder rows
     # (csrc/pwg_vq.hip)
     "pwg_vq_wave_rows",
@@ -167,6 +174,11 @@ PWG_OPT_SKIP_AHEAD = 10
 
 
 PWG_VQ_BAD_CODE, PWG_VQ_BAD_GLOBAL, PWG_VQ_BAD_INPUT = 1, 2, 4
+
+PWG_SINE_BAD_F0 = 1
+PWG_SINE_LAYOUTS = {"tile": 0, "hold": 1}
+PWG_SINE_MAX_DIM = 8
+PWG_SINE_SCAN_BLOCK = 1024
 
 PWG_SMG_MAX_SCALES = 16
 PWG_SMG_STATS_TILE = 128
@@ -413,6 +425,12 @@ def load():
         lib.pwg_embed_rows_f0.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ll, vp, vp, vp]
         lib.pwg_uhg_excite_rows.argtypes = [vp, vp, vp, ci, ci, ctypes.c_float, vp, ci, ll, vp, vp]
         cf = ctypes.c_float
+        lib.pwg_sine_scratch_bytes.argtypes = [ll, ci]
+        lib.pwg_sine_scratch_bytes.restype = ll
+        lib.pwg_sine_frames_scratch_bytes.argtypes = [ll, ci]
+        lib.pwg_sine_frames_scratch_bytes.restype = ll
+        lib.pwg_sine_samples.argtypes = [vp, vp, ci, ll, cf, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, ll, vp, vp]
+        lib.pwg_sine_frames.argtypes = [vp, vp, ci, ll, ci, ci, cf, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, ll, vp, vp]
         lib.pwg_vq_wave_rows.argtypes = [vp, vp, vp, ci, ci, cf, vp, vp, ci, ll, vp, vp]
         lib.pwg_vq_gsconv_packed_count.argtypes = [ci, ci, ci]
         lib.pwg_vq_gsconv_packed_count.restype = ll

@@ -20,7 +20,12 @@ Same arguments for the mel-to-wave case (--dumpdir with ``*-feats.npy`` files, -
     durations: no further device-to-host traffic);
   * UHiFiGANGenerator reads ``*-excitation.npy`` beside each ``*-feats.npy`` (bin/decode.py:188-192 of
     the reference) and fails before any decoding when one is missing; ``*-f0.npy`` is read if present
-    and otherwise ignored (the generator never uses f0, models/uhifigan.py:261-301);
+    and otherwise ignored (the generator never uses f0, models/uhifigan.py:261-301). With
+    --excitation-from-f0 {tile,hold} (an addition) no excitation dump is needed: ``*-f0.npy`` beside each
+    ``*-feats.npy`` is padded (edge) or trimmed to the mel length (bin/preprocess.py:427-430 of the reference)
+    and the excitation is generated on the GPU (UHiFiGANGenerator.inference_batch_from_f0) at
+    ``sampling_rate_for_feats`` if the config has it, else ``sampling_rate``; ``tile`` is the layout the
+    reference's preprocessing produces. --excitation-seed seeds the noise term's device draws;
   * VQVAE takes the reference's VQ-WAV2WAV branch (bin/decode.py:274-387) for ``format: npy`` dumps: it
     reads ``*-wave.npy`` (and ``*-local.npy`` / ``*-global.npy`` beside each when the config sets
     use_local_condition / use_global_condition), runs wav -> codes -> wav over ragged batches
@@ -92,6 +97,27 @@ def excitation_files(feats_files):
         raise FileNotFoundError(f"UHiFiGANGenerator needs an excitation dump beside every feature file: "
                                 f"{len(missing)} missing, first {missing[0]}")
     return paths
+
+
+def f0_files(feats_files):
+    """The ``*-f0.npy`` file beside each ``*-feats.npy`` (--excitation-from-f0); raises
+    FileNotFoundError naming the first utterances that lack one."""
+    paths = [f[:-len("-feats.npy")] + "-f0.npy" for f in feats_files]
+    missing = [p for p in paths if not os.path.exists(p)]
+    if missing:
+        raise FileNotFoundError(f"--excitation-from-f0 needs an f0 dump beside every feature file: "
+                                f"{len(missing)} missing, first {missing[0]}")
+    return paths
+
+
+def fit_f0(f0, frames):
+    """f0 trimmed, or padded with its last value, to the mel length (bin/preprocess.py:427-430)."""
+    f0 = np.ascontiguousarray(f0, np.float32).reshape(-1)
+    if len(f0) >= frames:
+        return f0[:frames]
+    if len(f0) == 0:
+        raise ValueError("an empty f0 contour cannot be padded")
+    return np.pad(f0, (0, frames - len(f0)), mode="edge")
 
 
 def vq_condition_files(wave_files, use_local, use_global):
@@ -177,6 +203,12 @@ def main(argv=None):
     ap.add_argument("--spk-id", type=int, default=None,
                     help="DiscreteSymbolStyleMelGANGenerator only: the speaker id of every utterance (replaces the "
                          "second column of the id files, which may then be (T,) or (T, 1))")
+    ap.add_argument("--excitation-from-f0", choices=("tile", "hold"), default=None,
+                    help="UHiFiGANGenerator only: generate the excitation on the GPU from *-f0.npy instead of reading "
+                         "*-excitation.npy (tile: the contour repeated hop times, as the reference's preprocessing; "
+                         "hold: every frame held for hop samples)")
+    ap.add_argument("--excitation-seed", type=int, default=None,
+                    help="with --excitation-from-f0: seed of the noise term's draws on the device")
     ap.add_argument("--batch-frames", type=int, default=None,
                     help="max mel frames per engine pass (ragged batch); default: sized from free device "
                          "memory (--batch-mem-frac of it, at most --batch-mem-gib)")
@@ -203,7 +235,14 @@ def main(argv=None):
         raise NotImplementedError("hdf5 dumps need h5py, which is not available; dump with format: npy")
 
     uhifigan = config.get("generator_type") == "UHiFiGANGenerator"
-    exc_files = excitation_files(find_files(args.dumpdir, "*-feats.npy")) if uhifigan else None
+    if args.excitation_from_f0 is not None and not uhifigan:
+        raise NotImplementedError(f"--excitation-from-f0 applies to a UHiFiGANGenerator (got "
+                                  f"{config.get('generator_type')})")
+    exc_files = exc_f0_files = None
+    if uhifigan and args.excitation_from_f0 is not None:
+        exc_f0_files = f0_files(find_files(args.dumpdir, "*-feats.npy"))
+    elif uhifigan:
+        exc_files = excitation_files(find_files(args.dumpdir, "*-feats.npy"))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = 0
@@ -247,6 +286,9 @@ def main(argv=None):
     lengths = [int(np.load(f, mmap_mode="r", allow_pickle=False).shape[0]) for f in files]
     logging.info(f"The number of features to be decoded = {len(files)}.")
     sr = config["sampling_rate"]
+    exc_sr = config.get("sampling_rate_for_feats") or sr
+    if exc_f0_files is not None and args.excitation_seed is not None:
+        torch.manual_seed(args.excitation_seed)
     if args.batch_frames is None:
         per_frame, per_utt, budget = batch_cost_model(model, device, args.batch_mem_frac, args.batch_mem_gib)
         logging.info(f"batch budget: {budget / 2**30:.2f} GiB, {per_frame:.0f} B per mel frame + {per_utt:.0f} B "
@@ -302,7 +344,9 @@ def main(argv=None):
                 kwargs["ds"] = [durations[i] for _, i in batch]
             if smg_tokens and args.spk_id is not None:
                 kwargs["g"] = args.spk_id
-            if uhifigan:
+            if exc_f0_files is not None:
+                f0s = [fit_f0(np.load(exc_f0_files[i], allow_pickle=False), lengths[i]) for _, i in batch]
+            elif uhifigan:
                 excs = [np.ascontiguousarray(np.load(exc_files[i], allow_pickle=False), np.float32).reshape(-1)
                         for _, i in batch]
                 for _, i in batch:  # read like the reference does, never used by the generator
@@ -311,7 +355,9 @@ def main(argv=None):
                         np.load(f0_path, allow_pickle=False)
             start = time.time()
             with torch.no_grad():
-                if uhifigan:
+                if exc_f0_files is not None:
+                    ys = model.inference_batch_from_f0(cs, f0s, exc_sr, args.excitation_from_f0)
+                elif uhifigan:
                     ys = model.inference_batch(cs, excs)
                 else:
                     ys = model.inference_batch(cs, normalize_before=args.normalize_before, **kwargs)

@@ -5,7 +5,10 @@ uhifigan.py:19-387): same constructor arguments and defaults, sub-module names a
 (input_conv.0, downsamples.i.0, downsamples_mrf.n, hidden_conv, upsamples.i.1, upsamples_mrf.n,
 output_conv.1), ``forward(c, f0, excitation)``, ``inference(excitation, f0, c, normalize_before)``,
 ``remove_weight_norm``, ``apply_weight_norm``, ``reset_parameters``, ``register_stats``; plus
-``inference_batch`` for ragged batches. Eval semantics: Dropout is the identity.
+``inference_batch`` for ragged batches, and ``excitation_from_f0`` / ``inference_from_f0`` /
+``inference_batch_from_f0``, which generate the excitation on the GPU from frame-rate f0 (the HIP sine
+generator pwg_sine_frames, include/pwg_sine.h: what the reference's preprocessing computes on the CPU
+with SineGen, bin/preprocess.py:420-442). Eval semantics: Dropout is the identity.
 
 The network is a U-Net (models/uhifigan.py:273-301). The excitation signal at the sample rate goes
 through input_conv (1 -> C; the HIP front end pwg_uhg_excite_rows, include/pwg_uhg.h, whose output is
@@ -268,7 +271,6 @@ class UHiFiGANGenerator(torch.nn.Module):
 
     def _run(self, cs, excs, keep=None):
         dev = self._device()
-        eng = self.engine()
         if len(cs) != len(excs) or not cs:
             raise ValueError("one excitation per utterance is required")
         hop = self.upsample_factor
@@ -280,9 +282,15 @@ class UHiFiGANGenerator(torch.nn.Module):
             if e.numel() != c.size(0) * hop:
                 raise ValueError(f"excitation has {e.numel()} samples, expected T * prod(upsample_scales) = "
                                  f"{c.size(0)} * {hop} = {c.size(0) * hop}")
+        exc = torch.cat(excs).contiguous() if len(excs) > 1 else excs[0].contiguous()
+        return self._run_packed(cs, exc, keep)
+
+    def _run_packed(self, cs, exc, keep=None):
+        """The body over device mels ``cs`` and the packed excitation rows of the whole batch."""
+        dev = self._device()
+        eng = self.engine()
         frames = [int(c.size(0)) for c in cs]
         mel = torch.cat([c.reshape(-1) for c in cs]) if len(cs) > 1 else cs[0].reshape(-1)
-        exc = torch.cat(excs).contiguous() if len(excs) > 1 else excs[0].contiguous()
         ext, row_start = self._excite(exc, frames, dev)
         outs = eng.infer_rows(frames, mel, ext=ext)
         if keep is not None:
@@ -315,3 +323,76 @@ class UHiFiGANGenerator(torch.nn.Module):
         """Ragged batch: lists of (T_u, in_channels) and (T_u * hop,) -> list of (T_u * hop, out_channels);
         one plan for the batch."""
         return self._run(list(cs), list(excitations))
+
+    # ------------------------------------------------------------------ excitation from f0
+    @staticmethod
+    def _check_sine_args(sampling_rate, layout):
+        if layout not in _lib.PWG_SINE_LAYOUTS:
+            raise ValueError(f"layout must be 'tile' or 'hold', got {layout!r}")
+        if not sampling_rate > 0:
+            raise ValueError(f"sampling_rate must be positive, got {sampling_rate}")
+
+    def _sine_frames(self, f0s, sampling_rate, layout, noises, generator, dev):
+        """One pwg_sine_frames launch over the ragged batch: the packed excitation rows (sum T_u * hop,)
+        ``_excite`` reads, on the device, and the frames per utterance. SineGen's defaults, as the
+        reference's preprocessing uses them: one channel, sine_amp 0.1, noise_std 0.003, threshold 0."""
+        from . import sinegen
+
+        f0s = [torch.as_tensor(f, dtype=torch.float32).to(dev).reshape(-1) for f in f0s]
+        if not f0s:
+            raise ValueError("one f0 contour per utterance is required")
+        hop = self.upsample_factor
+        frames = [int(f.numel()) for f in f0s]
+        starts = np.zeros(len(frames) + 1, np.int64)
+        np.cumsum(frames, out=starts[1:])
+        rows = int(starts[-1]) * hop
+        if noises is None:
+            n = torch.randn(rows, device=dev, generator=generator)
+        else:
+            if len(noises) != len(f0s):
+                raise ValueError("one noise signal per utterance is required")
+            noises = [torch.as_tensor(z, dtype=torch.float32).to(dev).reshape(-1) for z in noises]
+            for z, t in zip(noises, frames):
+                if z.numel() != t * hop:
+                    raise ValueError(f"noise has {z.numel()} samples, expected T * prod(upsample_scales) = {t * hop}")
+            n = torch.cat(noises) if len(noises) > 1 else noises[0].contiguous()
+        f0 = torch.cat(f0s) if len(f0s) > 1 else f0s[0].contiguous()
+        exc = torch.empty(rows, dtype=torch.float32, device=dev)
+        flag = sinegen.sine_call("pwg_sine_frames", dev, f0, torch.from_numpy(starts).to(dev), len(frames),
+                                 int(starts[-1]), (hop, _lib.PWG_SINE_LAYOUTS[layout]), float(sampling_rate), 1, 0.1,
+                                 0.003, 0.0, None, n, exc, None, None)
+        sinegen.check_flag(flag)
+        return exc, frames
+
+    def excitation_from_f0(self, f0s, sampling_rate, layout="tile", noise=None, generator=None):
+        """Frame-rate f0 contours (list of (T_u,)) -> list of (T_u * hop,) excitation signals on the
+        device, what the reference dumps as ``*-excitation.npy``. layout "tile" repeats the whole
+        contour hop times (ext[i] = f0[i % T], what the reference's preprocessing builds and shipped
+        checkpoints were trained on), "hold" holds every frame for hop samples (ext[i] = f0[i // hop]).
+        noise: list of (T_u * hop,) standard-normal draws; otherwise drawn on the device with
+        ``generator`` (a stream that differs from CPU torch's)."""
+        self._check_sine_args(sampling_rate, layout)
+        exc, frames = self._sine_frames(list(f0s), sampling_rate, layout, noise, generator, self._device())
+        return list(torch.split(exc, [t * self.upsample_factor for t in frames]))
+
+    def inference_from_f0(self, f0, c, sampling_rate, layout="tile", noise=None):
+        """``inference`` with the excitation generated from f0 (T,) on the GPU: c (T, in_channels) ->
+        (T * hop, out_channels)."""
+        return self.inference_batch_from_f0([c], [f0], sampling_rate, layout, None if noise is None else [noise])[0]
+
+    def inference_batch_from_f0(self, cs, f0s, sampling_rate, layout="tile", noises=None):
+        """``inference_batch`` with the excitations generated from the f0 contours: one pwg_sine_frames
+        launch writes the packed rows the front end reads (no host round trip)."""
+        self._check_sine_args(sampling_rate, layout)
+        dev = self._device()
+        cs, f0s = list(cs), list(f0s)
+        if len(cs) != len(f0s) or not cs:
+            raise ValueError("one f0 contour per utterance is required")
+        cs = [torch.as_tensor(c, dtype=torch.float32).to(dev).contiguous() for c in cs]
+        for c, f in zip(cs, f0s):
+            if c.dim() != 2 or c.size(1) != self.in_channels:
+                raise ValueError(f"c must be (T, {self.in_channels})")
+            if int(np.prod(np.shape(f))) != c.size(0):
+                raise ValueError(f"f0 has {int(np.prod(np.shape(f)))} frames, c has {c.size(0)}")
+        exc, _ = self._sine_frames(f0s, sampling_rate, layout, noises, None, dev)
+        return self._run_packed(cs, exc)
