@@ -20,12 +20,16 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
                             *_from_f0 methods
   VQVAE                     drop-in VQ-VAE (waveform -> codes -> waveform): HIP grouped strided encoder
                             levels, nearest-code search and decoder front end (include/pwg_vq.h)
+  MelSpectrogram, logmelfilterbank, LogMelExtractor
+                            waveform -> (normalised) log-mel features: the STFT as a windowed-DFT GEMM fused
+                            with magnitude, mel projection, log and normalisation (include/pwg_mel.h)
 """
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
 from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
 from .dsym_stylemelgan import DiscreteSymbolStyleMelGANGenerator  # noqa: F401
 from .dsym_variants import DiscreteSymbolDurationGenerator, DiscreteSymbolF0Generator  # noqa: F401
+from .logmel import LogMelExtractor, MelSpectrogram, logmelfilterbank, slaney_mel_basis  # noqa: F401
 from .models import ParallelWaveGANGenerator  # noqa: F401
 from .sinegen import SineGen  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401

@@ -33,11 +33,13 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_uconv.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_vq.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_sine.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_mel.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
     os.path.join(REPO_DIR, "include", "pwg_cnet.h"),
     os.path.join(REPO_DIR, "include", "pwg_embed.h"),
+    os.path.join(REPO_DIR, "include", "pwg_mel.h"),
     os.path.join(REPO_DIR, "include", "pwg_sine.h"),
     os.path.join(REPO_DIR, "include", "pwg_smg.h"),
     os.path.join(REPO_DIR, "include", "pwg_uhg.h"),
@@ -131,6 +133,11 @@ EXPORTED_SYMBOLS = (
     "pwg_sine_frames_scratch_bytes",
     "pwg_sine_samples",
     "pwg_sine_frames",
+    # include/pwg_mel.h: log-mel feature extraction (csrc/pwg_mel.hip)
+    "pwg_mel_frames",
+    "pwg_mel_plan_create",
+    "pwg_mel_plan_destroy",
+    "pwg_mel_run",
     # include/pwg_vq.h: VQVAE's encoder front end, grouped strided levels, code search and decoder rows
     # (csrc/pwg_vq.hip)
     "pwg_vq_wave_rows",
@@ -179,6 +186,10 @@ PWG_SINE_BAD_F0 = 1
 PWG_SINE_LAYOUTS = {"tile": 0, "hold": 1}
 PWG_SINE_MAX_DIM = 8
 PWG_SINE_SCAN_BLOCK = 1024
+
+PWG_MEL_FRAME_TILE = 64
+PWG_MEL_MAX_MELS = 128
+PWG_MEL_WINDOW_HANN = 0
 
 PWG_SMG_MAX_SCALES = 16
 PWG_SMG_STATS_TILE = 128
@@ -431,6 +442,12 @@ def load():
         lib.pwg_sine_frames_scratch_bytes.restype = ll
         lib.pwg_sine_samples.argtypes = [vp, vp, ci, ll, cf, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, ll, vp, vp]
         lib.pwg_sine_frames.argtypes = [vp, vp, ci, ll, ci, ci, cf, ci, cf, cf, cf, vp, vp, vp, vp, vp, vp, ll, vp, vp]
+        lib.pwg_mel_frames.argtypes = [ll, ci]
+        lib.pwg_mel_frames.restype = ll
+        lib.pwg_mel_plan_create.argtypes = [ci, ci, ci, ci, ci, vp, ll, cf, cf, ci, vp, vp, ctypes.POINTER(vp)]
+        lib.pwg_mel_plan_destroy.argtypes = [vp]
+        lib.pwg_mel_plan_destroy.restype = None
+        lib.pwg_mel_run.argtypes = [vp, vp, ctypes.POINTER(ll), ci, vp, ll, vp]
         lib.pwg_vq_wave_rows.argtypes = [vp, vp, vp, ci, ci, cf, vp, vp, ci, ll, vp, vp]
         lib.pwg_vq_gsconv_packed_count.argtypes = [ci, ci, ci]
         lib.pwg_vq_gsconv_packed_count.restype = ll

@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""Dump log-mel features of a directory of wavs with the MI355X engine: the mel branch of the
+``parallel-wavegan-preprocess`` CLI (parallel_wavegan/bin/preprocess.py:348-405, 454-493) and, with
+--stats, of ``parallel-wavegan-normalize`` (bin/normalize.py), for ``format: npy``.
+
+    python -m parallelwavegan_amd.bin.preprocess --rootdir WAVS --dumpdir DUMP --config conf.yml [--stats stats.npy]
+
+Every ``*.wav`` under --rootdir (PCM16 mono, at the config's sampling_rate) gives ``<utt>-feats.npy``
+((frames, num_mels) float32) and ``<utt>-wave.npy`` (the audio edge-padded by fft_size and cut to
+frames * hop_size samples, float32): the files the decode CLI reads. With --stats the features are
+``(logmel - mean) / scale``, as bin/normalize.py writes them. The utterances are extracted in ragged
+batches of up to --batch-samples samples per kernel launch.
+
+Not available, each raising with a message: --scp / --segments (kaldiio), hdf5 dumps, silence trimming,
+resampling (sampling_rate_for_feats), a global gain, f0 / excitation extraction, and a window other
+than hann.
+"""
+
+import argparse
+import logging
+import os
+import sys
+
+import numpy as np
+
+
+def _check_header(path, w):
+    if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+        raise ValueError(f"{path}: only 16 bit PCM wavs are read (sample width {w.getsampwidth()} bytes)")
+    if w.getnchannels() != 1:
+        raise ValueError(f"{path} seems to be multi-channel signal.")
+
+
+def wav_header(path):
+    """(samples, sampling rate) of a PCM16 mono wav, from its header alone."""
+    import wave
+
+    with wave.open(path, "rb") as w:
+        _check_header(path, w)
+        return w.getnframes(), w.getframerate()
+
+
+def read_wav(path):
+    """(float32 samples in [-1, 1), sampling rate) of a PCM16 mono wav, scaled by 1 / 32768 as soundfile does."""
+    import wave
+
+    with wave.open(path, "rb") as w:
+        _check_header(path, w)
+        data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+        return data.astype(np.float32) / 32768.0, w.getframerate()
+
+
+def check_config(config):
+    """Raise for what this CLI leaves out."""
+    if config.get("format", "npy") != "npy":
+        raise NotImplementedError("hdf5 dumps need h5py, which is not available; dump with format: npy")
+    if config.get("trim_silence", False):
+        raise NotImplementedError("trim_silence needs librosa.effects.trim, which is not available; trim beforehand "
+                                  "and set trim_silence: false")
+    if "sampling_rate_for_feats" in config:
+        raise NotImplementedError("sampling_rate_for_feats needs resampling, which is not available")
+    if float(config.get("global_gain_scale", 1.0) or 0.0) not in (0.0, 1.0):
+        raise NotImplementedError("global_gain_scale other than 1.0 is not applied here; scale the wavs beforehand")
+    if config.get("use_f0") or config.get("use_f0_and_excitation"):
+        raise NotImplementedError("f0 / excitation extraction is not available; dump *-f0.npy with another tool")
+    if config.get("window", "hann") != "hann":
+        raise NotImplementedError(f"window {config['window']!r} is not accelerated (hann only)")
+
+
+def fit_audio(audio, frames, fft_size, hop_size):
+    """bin/preprocess.py:403-405: the audio edge-padded by fft_size and cut to frames * hop_size."""
+    audio = np.pad(audio, (0, fft_size), mode="edge")[: frames * hop_size]
+    assert len(audio) == frames * hop_size
+    return audio
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Dump log-mel features with the MI355X engine.")
+    ap.add_argument("--wav-scp", "--scp", default=None, type=str)
+    ap.add_argument("--segments", default=None, type=str)
+    ap.add_argument("--rootdir", default=None, type=str)
+    ap.add_argument("--dumpdir", type=str, required=True)
+    ap.add_argument("--config", type=str, required=True)
+    ap.add_argument("--stats", default=None, type=str, help="stats.npy ((2, num_mels): mean, scale): normalise")
+    ap.add_argument("--batch-samples", type=int, default=1 << 23, help="max samples per kernel launch")
+    ap.add_argument("--verbose", type=int, default=1)
+    args = ap.parse_args(argv)
+
+    level = logging.DEBUG if args.verbose > 1 else (logging.INFO if args.verbose > 0 else logging.WARN)
+    logging.basicConfig(level=level, format="%(asctime)s (%(module)s:%(lineno)d) %(levelname)s: %(message)s")
+
+    from parallelwavegan_amd.logmel import LogMelExtractor
+    from parallelwavegan_amd.utils import find_files, read_config
+
+    if args.wav_scp is not None or args.segments is not None:
+        raise NotImplementedError("--wav-scp/--scp/--segments need kaldiio, which is not available; use --rootdir")
+    if args.rootdir is None:
+        raise ValueError("Please specify --rootdir.")
+    config = read_config(args.config)
+    check_config(config)
+    stats = None
+    if args.stats is not None:
+        if not args.stats.endswith(".npy"):
+            raise NotImplementedError("hdf5 statistics need h5py, which is not available; use a stats.npy")
+        stats = np.load(args.stats, allow_pickle=False)
+    extractor = LogMelExtractor.from_config(config, stats=stats)
+    sr, fft_size, hop = config["sampling_rate"], config["fft_size"], config["hop_size"]
+
+    files = find_files(args.rootdir, "*.wav")
+    logging.info(f"The number of files = {len(files)}.")
+    lengths = []
+    for f in files:  # headers only: every refusal comes before the first sample is read or file written
+        n, fs = wav_header(f)
+        if fs != sr:
+            raise ValueError(f"{f} seems to have a different sampling rate ({fs} Hz, the config says {sr} Hz).")
+        if n <= fft_size // 2:
+            raise ValueError(f"{f} has {n} samples: too short for fft_size {fft_size}")
+        lengths.append(n)
+    os.makedirs(args.dumpdir, exist_ok=True)
+
+    def flush(batch):
+        """Load, extract and write one batch of file indices; only its samples are in memory."""
+        audios = [read_wav(files[i])[0] for i in batch]
+        mels = extractor.extract_batch(audios)
+        for i, audio, mel in zip(batch, audios, mels):
+            utt_id = os.path.splitext(os.path.basename(files[i]))[0]
+            mel = mel.cpu().numpy()
+            np.save(os.path.join(args.dumpdir, f"{utt_id}-wave.npy"),
+                    fit_audio(audio, len(mel), fft_size, hop).astype(np.float32), allow_pickle=False)
+            np.save(os.path.join(args.dumpdir, f"{utt_id}-feats.npy"), mel.astype(np.float32), allow_pickle=False)
+
+    batch, n = [], 0
+    for i, t in enumerate(lengths):
+        if batch and n + t > args.batch_samples:
+            flush(batch)
+            batch, n = [], 0
+        batch.append(i)
+        n += t
+    if batch:
+        flush(batch)
+    logging.info(f"wrote {len(files)} utterances to {args.dumpdir}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
