@@ -23,6 +23,9 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
   MelSpectrogram, logmelfilterbank, LogMelExtractor
                             waveform -> (normalised) log-mel features: the STFT as a windowed-DFT GEMM fused
                             with magnitude, mel projection, log and normalisation (include/pwg_mel.h)
+  yin_estimate, f0_torchyin, YinF0Extractor
+                            waveform -> frame-rate f0 contour: the YIN difference function in the direct form,
+                            prefix sum and first-minimum search in one kernel (include/pwg_yin.h)
 """
 
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
@@ -35,5 +38,6 @@ from .sinegen import SineGen  # noqa: F401
 from .stylemelgan import StyleMelGANGenerator  # noqa: F401
 from .uhifigan import UHiFiGANGenerator  # noqa: F401
 from .vqvae import VQVAE  # noqa: F401
+from .yin import YinF0Extractor, f0_torchyin, yin_estimate  # noqa: F401
 
 __version__ = "0.1.0"

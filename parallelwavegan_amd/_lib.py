@@ -34,6 +34,7 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_vq.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_sine.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_mel.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_yin.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
@@ -44,6 +45,7 @@ HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg_smg.h"),
     os.path.join(REPO_DIR, "include", "pwg_uhg.h"),
     os.path.join(REPO_DIR, "include", "pwg_vq.h"),
+    os.path.join(REPO_DIR, "include", "pwg_yin.h"),
     os.path.join(PKG_DIR, "csrc", "pwg_internal.h"),
 ]
 OFFLOAD_ARCH = "gfx950"
@@ -138,6 +140,11 @@ EXPORTED_SYMBOLS = (
     "pwg_mel_plan_create",
     "pwg_mel_plan_destroy",
     "pwg_mel_run",
+    # include/pwg_yin.h: YIN f0 estimation (csrc/pwg_yin.hip)
+    "pwg_yin_frames",
+    "pwg_yin_plan_create",
+    "pwg_yin_plan_destroy",
+    "pwg_yin_run",
     # include/pwg_vq.h: VQVAE's encoder front end, grouped strided levels, code search and decoder rows
     # (csrc/pwg_vq.hip)
     "pwg_vq_wave_rows",
@@ -190,6 +197,9 @@ PWG_SINE_SCAN_BLOCK = 1024
 PWG_MEL_FRAME_TILE = 64
 PWG_MEL_MAX_MELS = 128
 PWG_MEL_WINDOW_HANN = 0
+
+PWG_YIN_FRAME_TILE = 8
+PWG_YIN_MAX_TAU = 1680
 
 PWG_SMG_MAX_SCALES = 16
 PWG_SMG_STATS_TILE = 128
@@ -448,6 +458,12 @@ def load():
         lib.pwg_mel_plan_destroy.argtypes = [vp]
         lib.pwg_mel_plan_destroy.restype = None
         lib.pwg_mel_run.argtypes = [vp, vp, ctypes.POINTER(ll), ci, vp, ll, vp]
+        lib.pwg_yin_frames.argtypes = [ll, ci, ci]
+        lib.pwg_yin_frames.restype = ll
+        lib.pwg_yin_plan_create.argtypes = [cf, ci, ci, ci, cf, ci, ctypes.POINTER(vp)]
+        lib.pwg_yin_plan_destroy.argtypes = [vp]
+        lib.pwg_yin_plan_destroy.restype = None
+        lib.pwg_yin_run.argtypes = [vp, vp, ctypes.POINTER(ll), ci, ctypes.POINTER(ll), vp, vp, vp, ll, vp]
         lib.pwg_vq_wave_rows.argtypes = [vp, vp, vp, ci, ci, cf, vp, vp, ci, ll, vp, vp]
         lib.pwg_vq_gsconv_packed_count.argtypes = [ci, ci, ci]
         lib.pwg_vq_gsconv_packed_count.restype = ll

@@ -4,6 +4,7 @@
 --stats, of ``parallel-wavegan-normalize`` (bin/normalize.py), for ``format: npy``.
 
     python -m parallelwavegan_amd.bin.preprocess --rootdir WAVS --dumpdir DUMP --config conf.yml [--stats stats.npy]
+                                                 [--extract-f0-yin]
 
 Every ``*.wav`` under --rootdir (PCM16 mono, at the config's sampling_rate) gives ``<utt>-feats.npy``
 ((frames, num_mels) float32) and ``<utt>-wave.npy`` (the audio edge-padded by fft_size and cut to
@@ -11,9 +12,17 @@ frames * hop_size samples, float32): the files the decode CLI reads. With --stat
 ``(logmel - mean) / scale``, as bin/normalize.py writes them. The utterances are extracted in ragged
 batches of up to --batch-samples samples per kernel launch.
 
+With --extract-f0-yin every utterance also gives ``<utt>-f0.npy``: the (frames,) float32 log-f0 contour of
+the YIN estimator (parallelwavegan_amd.yin, the reference's f0_torchyin call of bin/preprocess.py:420-430
+with frame_length = win_length), computed on the fitted audio of ``<utt>-wave.npy`` in the same ragged
+batches and fitted to the mel length by a cut or a hold of the last value; 0 marks an unvoiced frame. No
+``<utt>-excitation.npy`` is written: ``decode --excitation-from-f0 tile`` generates the excitation from
+the f0 on the GPU, and the reference's dump of it holds random noise in any case. The flag is opt-in and
+separate from the reference's --extract-f0 (its pyreaper path, not available here).
+
 Not available, each raising with a message: --scp / --segments (kaldiio), hdf5 dumps, silence trimming,
-resampling (sampling_rate_for_feats), a global gain, f0 / excitation extraction, and a window other
-than hann.
+resampling (sampling_rate_for_feats), a global gain, the config keys use_f0 / use_f0_and_excitation (use
+--extract-f0-yin), and a window other than hann.
 """
 
 import argparse
@@ -83,6 +92,8 @@ def main(argv=None):
     ap.add_argument("--config", type=str, required=True)
     ap.add_argument("--stats", default=None, type=str, help="stats.npy ((2, num_mels): mean, scale): normalise")
     ap.add_argument("--batch-samples", type=int, default=1 << 23, help="max samples per kernel launch")
+    ap.add_argument("--extract-f0-yin", action="store_true",
+                    help="also write <utt>-f0.npy: the YIN log-f0 contour, fitted to the mel length")
     ap.add_argument("--verbose", type=int, default=1)
     args = ap.parse_args(argv)
 
@@ -104,6 +115,11 @@ def main(argv=None):
             raise NotImplementedError("hdf5 statistics need h5py, which is not available; use a stats.npy")
         stats = np.load(args.stats, allow_pickle=False)
     extractor = LogMelExtractor.from_config(config, stats=stats)
+    f0_extractor = None
+    if args.extract_f0_yin:
+        from parallelwavegan_amd.yin import YinF0Extractor
+
+        f0_extractor = YinF0Extractor.from_config(config)  # raises for a geometry it cannot take, before any write
     sr, fft_size, hop = config["sampling_rate"], config["fft_size"], config["hop_size"]
 
     files = find_files(args.rootdir, "*.wav")
@@ -122,12 +138,18 @@ def main(argv=None):
         """Load, extract and write one batch of file indices; only its samples are in memory."""
         audios = [read_wav(files[i])[0] for i in batch]
         mels = extractor.extract_batch(audios)
-        for i, audio, mel in zip(batch, audios, mels):
+        fitted = [fit_audio(audio, len(mel), fft_size, hop).astype(np.float32) for audio, mel in zip(audios, mels)]
+        f0s = [None] * len(batch)
+        if f0_extractor is not None:
+            f0s = f0_extractor.extract_batch(fitted, frames=[len(mel) for mel in mels])
+        for i, audio, mel, f0 in zip(batch, fitted, mels, f0s):
             utt_id = os.path.splitext(os.path.basename(files[i]))[0]
             mel = mel.cpu().numpy()
-            np.save(os.path.join(args.dumpdir, f"{utt_id}-wave.npy"),
-                    fit_audio(audio, len(mel), fft_size, hop).astype(np.float32), allow_pickle=False)
+            np.save(os.path.join(args.dumpdir, f"{utt_id}-wave.npy"), audio, allow_pickle=False)
             np.save(os.path.join(args.dumpdir, f"{utt_id}-feats.npy"), mel.astype(np.float32), allow_pickle=False)
+            if f0 is not None:
+                np.save(os.path.join(args.dumpdir, f"{utt_id}-f0.npy"), f0.cpu().numpy().astype(np.float32),
+                        allow_pickle=False)
 
     batch, n = [], 0
     for i, t in enumerate(lengths):
