@@ -26,8 +26,12 @@ Public surface (mirrors parallel_wavegan.models for the generator hot path):
   yin_estimate, f0_torchyin, YinF0Extractor
                             waveform -> frame-rate f0 contour: the YIN difference function in the direct form,
                             prefix sum and first-minimum search in one kernel (include/pwg_yin.h)
+  trim_silence, resample, resample_poly, kaiser_lowpass_taps, AudioConditioner
+                            the preprocess's waveform steps: silence trim, polyphase resampling, and the fit to
+                            the feature length with the global gain and the clipping peak (include/pwg_wave.h)
 """
 
+from .audio import AudioConditioner, kaiser_lowpass_taps, resample, resample_poly, trim_silence  # noqa: F401
 from .engine import Engine, GraphedRun, HostHandle  # noqa: F401
 from .dsym import DiscreteSymbolHiFiGANGenerator  # noqa: F401
 from .dsym_stylemelgan import DiscreteSymbolStyleMelGANGenerator  # noqa: F401

@@ -35,6 +35,7 @@ CSRC = [
     os.path.join(PKG_DIR, "csrc", "pwg_sine.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_mel.hip"),
     os.path.join(PKG_DIR, "csrc", "pwg_yin.hip"),
+    os.path.join(PKG_DIR, "csrc", "pwg_wave.hip"),
 ]
 HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg.h"),
@@ -45,6 +46,7 @@ HEADERS = [
     os.path.join(REPO_DIR, "include", "pwg_smg.h"),
     os.path.join(REPO_DIR, "include", "pwg_uhg.h"),
     os.path.join(REPO_DIR, "include", "pwg_vq.h"),
+    os.path.join(REPO_DIR, "include", "pwg_wave.h"),
     os.path.join(REPO_DIR, "include", "pwg_yin.h"),
     os.path.join(PKG_DIR, "csrc", "pwg_internal.h"),
 ]
@@ -145,6 +147,17 @@ EXPORTED_SYMBOLS = (
     "pwg_yin_plan_create",
     "pwg_yin_plan_destroy",
     "pwg_yin_run",
+    # include/pwg_wave.h: silence trim, polyphase resampling, fit / gain / peak (csrc/pwg_wave.hip)
+    "pwg_trim_frames",
+    "pwg_trim_plan_create",
+    "pwg_trim_plan_destroy",
+    "pwg_trim_run",
+    "pwg_resample_out_len",
+    "pwg_resample_plan_create",
+    "pwg_resample_plan_destroy",
+    "pwg_resample_plan_tile",
+    "pwg_resample_run",
+    "pwg_wave_fit_run",
     # include/pwg_vq.h: VQVAE's encoder front end, grouped strided levels, code search and decoder rows
     # (csrc/pwg_vq.hip)
     "pwg_vq_wave_rows",
@@ -200,6 +213,13 @@ PWG_MEL_WINDOW_HANN = 0
 
 PWG_YIN_FRAME_TILE = 8
 PWG_YIN_MAX_TAU = 1680
+
+PWG_TRIM_PAD_MODES = {"constant": 0, "reflect": 1}
+PWG_TRIM_FRAME_TILE = 16
+PWG_TRIM_MAX_TILE_SPAN = 36864
+PWG_RESAMPLE_MAX_RATE = 640
+PWG_RESAMPLE_MAX_TAPS = 20 * 640 + 1
+PWG_RESAMPLE_OUT_TILE = 1024
 
 PWG_SMG_MAX_SCALES = 16
 PWG_SMG_STATS_TILE = 128
@@ -464,6 +484,20 @@ def load():
         lib.pwg_yin_plan_destroy.argtypes = [vp]
         lib.pwg_yin_plan_destroy.restype = None
         lib.pwg_yin_run.argtypes = [vp, vp, ctypes.POINTER(ll), ci, ctypes.POINTER(ll), vp, vp, vp, ll, vp]
+        lib.pwg_trim_frames.argtypes = [ll, ci, ci]
+        lib.pwg_trim_frames.restype = ll
+        lib.pwg_trim_plan_create.argtypes = [ci, ci, cf, ci, ctypes.POINTER(vp)]
+        lib.pwg_trim_plan_destroy.argtypes = [vp]
+        lib.pwg_trim_plan_destroy.restype = None
+        lib.pwg_trim_run.argtypes = [vp, vp, ctypes.POINTER(ll), ci, vp, vp, ll, vp]
+        lib.pwg_resample_out_len.argtypes = [ll, ci, ci]
+        lib.pwg_resample_out_len.restype = ll
+        lib.pwg_resample_plan_create.argtypes = [ci, ci, vp, ci, ctypes.POINTER(vp)]
+        lib.pwg_resample_plan_destroy.argtypes = [vp]
+        lib.pwg_resample_plan_destroy.restype = None
+        lib.pwg_resample_plan_tile.argtypes = [vp]
+        lib.pwg_resample_run.argtypes = [vp, vp, ctypes.POINTER(ll), ci, vp, ll, vp]
+        lib.pwg_wave_fit_run.argtypes = [vp, ctypes.POINTER(ll), ctypes.POINTER(ll), vp, ctypes.POINTER(ll), ci, cf, vp, vp]
         lib.pwg_vq_wave_rows.argtypes = [vp, vp, vp, ci, ci, cf, vp, vp, ci, ll, vp, vp]
         lib.pwg_vq_gsconv_packed_count.argtypes = [ci, ci, ci]
         lib.pwg_vq_gsconv_packed_count.restype = ll
